@@ -25,11 +25,15 @@ below the exchange, kept fact ROWS partitioned and exchanged in overlapped chunk
 `--exchange broadcast` = all-gather the dim, aggregate locally, exchange + merge the partial aggregates; the line
 times the other two strategies too (`exchange.alternative`, `exchange.alternative2`).
 
-Output: ONE JSON line on rank 0 (contract in the task description) with `roofline` (dominant kernel:
-HIP-event time per launch measured live on the ctx stream; and the operator-level pipeline figure),
+Output: ONE JSON line on rank 0 with `metric`, `value`, `unit`, `higher_is_better`, `dtype` and `ms_per_step` (the mean
+wall-clock time of the K = --steps timed steps between two barriers).  A plain run does only that: it sets up, warms up,
+times the K steps, writes the last step's result with --dump-outputs DIR and prints the line (`roofline` and
+`cpu_baseline` are null).  With --full the line also carries `roofline` (dominant kernel: HIP-event time per launch
+measured live on the ctx stream in profiled steps of their own; and the operator-level pipeline figure),
 `cpu_baseline` (all-core CPU port + the single-threaded restatement of the reference, on bounded samples),
-and at N = 1 `c5_variants` (sparse keys, three operators, duplicate build keys, GROUP BY a dim attribute, adversarial inputs) and `operators` (C2 / C3 / C4 / Order).
-Every result is checked per group before it is timed.
+`ms_per_step_each` / `ms_per_step_processes`, at N > 1 the profiled exchange figures and the other strategies, and at
+N = 1 `c5_variants` (sparse keys, three operators, duplicate build keys, GROUP BY a dim attribute, adversarial inputs) and
+`operators` (C2 / C3 / C4 / Order); with --full every result is checked per group before it is timed.
 """
 from __future__ import annotations
 
@@ -47,6 +51,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s peak
+DUMP_MAX_ROWS = 1 << 21  # --dump-outputs: 3 float64 columns x 2^21 rows = 48 MiB (the budget is 64 MB)
 
 
 def log(*a):
@@ -90,14 +95,25 @@ def parse():
     p.add_argument("--operators", action="store_true", help="(default at N=1; kept for old command lines)")
     p.add_argument("--no-operators", action="store_true",
                    help="skip the per-operator configs C2/C3/C4/Order and the C5 variants (sparse keys, three "
-                        "operators) that the default N=1 run times after the headline measurement")
+                        "operators) that the --full N=1 run times after the headline measurement")
     p.add_argument("--cpu-threads", type=int, default=0, help="threads of the all-core CPU baseline (0 = all)")
     p.add_argument("--processes", type=int, default=3,
-                   help="N=1: ms_per_step is ALSO measured in this many fresh processes in total (this one + children run "
+                   help="N=1 with --full: ms_per_step is ALSO measured in this many fresh processes in total (this one + children run "
                         "after its own timed region); the line carries their min / median / max: the partition kernels' "
                         "time follows how the driver backs the big buffers, which differs from process to process")
     p.add_argument("--child", action="store_true", help=argparse.SUPPRESS)  # a --processes child: headline timing only
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure: the per-group result check, the K steps timed one by one, "
+                        "the profiled steps (per-kernel times, `roofline`), the other exchange strategies (N > 1), the fresh "
+                        "processes, the C5 variants, the operators and the CPU baseline.  Without it the run sets up, warms up, "
+                        "times the K steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the result batch of the last one to DIR/*.npy (float64, at most "
+                        f"{DUMP_MAX_ROWS:,} rows: a fixed seeded sample of a larger result; see dump_outputs)")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
 
 
 def free_port():
@@ -268,6 +284,60 @@ def check_groups(torch, dist, dev, out, exp_cnt, exp_sum, has_dim, key_of=None):
     return ok, groups, rows, msg
 
 
+def _result_columns(torch, dev, out):
+    g = out.num_rows
+    return [_tensor_view(torch, out.column(i).values, g, t, dev) for i, t in enumerate((torch.int64, torch.int64, torch.float64))]
+
+
+def result_totals(torch, dist, dev, out):
+    """(groups, joined rows = sum of COUNT) of the result batch `out` [key, COUNT, SUM], over all ranks when `dist`: what the
+    line's `config` reports when the per-group check (--full) did not count them"""
+    _, cnt, _ = _result_columns(torch, dev, out)
+    totals = torch.tensor([out.num_rows, int(cnt.sum().item()) if out.num_rows else 0], dtype=torch.int64, device=dev)
+    if dist is not None:
+        dist.all_reduce(totals)
+    groups, rows = [int(x) for x in totals.tolist()]
+    return groups, rows
+
+
+def dump_outputs(torch, dist, dev, out, path, rank, seed=0):
+    """--dump-outputs DIR: the result batch [d.key, COUNT(f.val), SUM(f.val)] of the last timed step, as a caller receives it,
+    written by rank 0 as float64 arrays DIR/groups_key.npy, groups_count.npy, groups_sum.npy (keys and counts are exact below
+    2^53) and DIR/summary.npy = [groups, joined rows, sum of SUM, rows written].  One GPU: the rows in the order the batch holds
+    them (first-seen order); N > 1: every rank's groups gathered on rank 0 and sorted by key (the ranks' results are disjoint and
+    have no order between them).  A result of more than DUMP_MAX_ROWS groups is written as a fixed seeded sample of its row
+    positions (`seed`, ascending), so that two builds given the same arguments write arrays that compare element by element."""
+    cols = _result_columns(torch, dev, out)
+    if dist is not None:
+        parts = [None] * dist.get_world_size() if rank == 0 else None
+        dist.gather_object([c.cpu().numpy() for c in cols], parts, dst=0)
+        if rank != 0:
+            return None
+        key, cnt, sm = [np.concatenate([p[i] for p in parts]) for i in range(3)]
+        order = np.argsort(key, kind="stable")
+        key, cnt, sm = key[order], cnt[order], sm[order]
+        g = key.size
+        summary = [g, int(cnt.sum()), float(sm.sum())]
+        if g > DUMP_MAX_ROWS:
+            pick = np.sort(np.random.default_rng(seed).choice(g, DUMP_MAX_ROWS, replace=False))
+            key, cnt, sm = key[pick], cnt[pick], sm[pick]
+    else:
+        g = out.num_rows
+        summary = [g, int(cols[1].sum().item()) if g else 0, float(cols[2].sum().item()) if g else 0.0]
+        if g > DUMP_MAX_ROWS:
+            pick = np.sort(np.random.default_rng(seed).choice(g, DUMP_MAX_ROWS, replace=False))
+            pick = torch.from_numpy(pick).to(dev)
+            cols = [c.index_select(0, pick) for c in cols]
+        key, cnt, sm = [c.cpu().numpy() for c in cols]
+    os.makedirs(path, exist_ok=True)
+    arrays = {"groups_key": key, "groups_count": cnt, "groups_sum": sm,
+              "summary": np.array(summary + [key.size], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
+    log(f"[bench] wrote {', '.join(n + '.npy' for n in arrays)} ({key.size:,} of {g:,} groups) to {path}")
+    return {"dir": path, "groups": g, "rows_written": int(key.size), "files": [n + ".npy" for n in arrays]}
+
+
 # algorithmic HBM bytes per launch of the kernels that can dominate (DESIGN.md §kernels)
 def algorithmic_bytes(kernel, w):
     nP, nB, s, M, G = w["fact_rows"], w["dim_rows"], w["selectivity"], w["matches"], w["groups"]
@@ -387,9 +457,10 @@ def main():
     if rank == 0:
         log(f"[bench] generated {f_hi - f_lo:,} fact rows + {d_hi - d_lo:,} dim rows per rank in {time.time() - t0:.1f}s")
     # expected result per group, computed by torch on the same columns (independent of the library):
-    # exp_cnt[k] / exp_sum[k] over the kept fact rows of ALL ranks, has_dim[k] = key k has a build partner
-    exp_cnt, exp_sum, has_dim, expected_kept = expected_groups(torch, dist if multi else None, fact_key, fact_val,
-                                                               dim_key, args.threshold, n_dim_total)
+    # exp_cnt[k] / exp_sum[k] over the kept fact rows of ALL ranks, has_dim[k] = key k has a build partner (--full)
+    if args.full:
+        exp_cnt, exp_sum, has_dim, expected_kept = expected_groups(torch, dist if multi else None, fact_key, fact_val,
+                                                                   dim_key, args.threshold, n_dim_total)
 
     pipe = Pipeline(be, abi, args.threshold, fused=not args.unfused, fuse_filter=not args.separate_filter)
 
@@ -681,25 +752,28 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    # ---- warmup (also validates the result once)
+    # ---- warmup (with --full it also validates the result once)
     out = None
     for _ in range(max(args.warmup, 1)):
         if out is not None:
             out.release()
         out = one_step()
-    out_groups_local = out.num_rows
-    ok, ngroups, got_rows, msg = check_groups(torch, dist if multi else None, dev, out, exp_cnt, exp_sum, has_dim)
-    if rank == 0:
-        log(f"[bench] check (per group: keys, COUNT bit-exact, SUM 1e-9 rel): {msg} -> {'OK' if ok else 'MISMATCH'}")
-    if not ok:
-        raise SystemExit("bench result check failed")
+    if args.full:
+        ok, ngroups, got_rows, msg = check_groups(torch, dist if multi else None, dev, out, exp_cnt, exp_sum, has_dim)
+        if rank == 0:
+            log(f"[bench] check (per group: keys, COUNT bit-exact, SUM 1e-9 rel): {msg} -> {'OK' if ok else 'MISMATCH'}")
+        if not ok:
+            raise SystemExit("bench result check failed")
     out.release()
 
-    # ---- timed region: exactly K steps between barriers
+    # ---- timed region: exactly K steps between barriers (the last step's result is kept for the line and --dump-outputs)
     barrier()
     t_start = time.perf_counter()
+    out = None
     for _ in range(args.steps):
-        one_step().release()
+        if out is not None:
+            out.release()
+        out = one_step()
     barrier()
     elapsed = time.perf_counter() - t_start
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -708,6 +782,85 @@ def main():
     elapsed = el.item()
     ms_per_step = elapsed / args.steps * 1e3
     value = n_fact_total / (elapsed / args.steps) / 1e6
+    out_groups_local = out.num_rows
+    if not args.full:  # (--full: the check above counted them)
+        ngroups, got_rows = result_totals(torch, dist if multi else None, dev, out)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(torch, dist if multi else None, dev, out, args.dump_outputs, rank)
+    out.release()
+
+    def exchange_base():
+        return {"strategy": strategy, "chunks": n_chunks if strategy == "partition" else 1,
+                "impl": ("C ABI (exchange.hip, RCCL on the ctx stream, no torch on the data path): sqlrs_exchange_all_to_all for "
+                         "single-chunk exchanges, sqlrs_exchange_begin / send_chunk / finish for the chunked fact rows"
+                         if abi_x["h"] is not None else "torch.distributed"),
+                "fused_filter_partition": bool(fused_exchange and strategy == "partition"), "ranks": rank_info}
+
+    def emit_line(roofline=None, cpu=None, step_times=None, processes=None, operators=None, variants=None, exchange_info=None):
+        line = {
+            "metric": "Mrows/sec for filter->hash-join->group-by pipeline; achieved HBM GB/s vs peak",
+            "value": round(value, 1), "unit": "Mrows/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None, "dtype": "int64 keys / f64 sum", "data": "synthetic",
+            "config": {"workload": "C5 filter(val>0.5) -> hash-join(fact x dim on int64 key) -> group-by(key) COUNT,SUM(f64)",
+                       "fact_rows": n_fact_total, "dim_rows": n_dim_total, "groups": int(ngroups),
+                       "selectivity": round(got_rows / n_fact_total, 4),
+                       "operators": "Filter -> HashJoin -> HashAgg (3 operators)" if args.unfused else
+                       "Filter -> HashJoinAgg (HashAgg fused over the Inner HashJoin)" if args.separate_filter else
+                       "HashJoinAgg with the probe-side Filter handed to it (sqlrs_join_agg_set_probe_filter): "
+                       f"filter evaluated inside the first partition pass = {bool(pipe.filter_fused_batches)}",
+                       "parallelism": ("single GPU" if not multi else
+                                       f"x{world}: all-gather dim, local partial aggregation, all-to-all of partial aggregates, merge"
+                                       if strategy == "broadcast" else
+                                       f"x{world}: partitioned hash join, partial aggregation below the exchange — dim hash-partitioned on the "
+                                       "join key + RCCL all-to-all; HashAgg(Filter(fact slice)) by key on every rank; partial aggregates "
+                                       "hash-partitioned + RCCL all-to-all; HashJoinAgg(dim partition, partials) on the owning rank"
+                                       if strategy == "combine" else
+                                       f"x{world}: partitioned hash join — Filter below the exchange, fact + dim hash-partitioned on "
+                                       f"the join key, RCCL all-to-all in {n_chunks} overlapped chunks, local HashJoinAgg"
+                                       + ("; Filter + partition fused in one pass (sqlrs_hash_partition_filter)" if fused_exchange else ""))},
+            "roofline": roofline, "cpu_baseline": cpu,
+            # probe batches of the last step that took the library's fused join + aggregate route / had the Filter
+            # evaluated inside the first partition pass (0 = the operators were composed: the 2.5x slower form)
+            "fused_batches": int(pipe.fused_batches), "filter_fused_batches": int(pipe.filter_fused_batches),
+            "full": bool(args.full),
+        }
+        if step_times:
+            line["ms_per_step_median"] = step_times["median"]
+            line["ms_per_step_each"] = step_times
+        if processes:
+            line["ms_per_step_processes"] = processes
+        if operators:
+            line["operators"] = operators
+        if variants:
+            line["c5_variants"] = variants
+        if exchange_info:
+            line["exchange"] = exchange_info
+        if dumped:
+            line["dump_outputs"] = dumped
+        if json_fd is not None:
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(line) + "\n").encode())
+        else:
+            print(json.dumps(line), flush=True)
+
+    def teardown():
+        if multi:
+            if abi_x["h"] is not None:
+                for old in abi_x["keep"]:
+                    old.release()
+                be.fn("exchange_destroy")(abi_x["h"])
+            dist.destroy_process_group()
+
+    if not args.full:  # a plain run: the headline line and nothing else
+        if args.child:  # a child of --processes: one number, nothing else
+            print(json.dumps({"ms_per_step": round(ms_per_step, 3)}), flush=True)
+        elif rank == 0:
+            emit_line(exchange_info=exchange_base() if multi else None)
+        teardown()
+        return
+
     # (review r05 #5) the same K steps once more, each timed on its own: median / min / max beside the contract's mean
     step_times = None
     if not multi:
@@ -740,19 +893,14 @@ def main():
     exchange_info = None
     if multi:  # SURVEY.md §8e scaling report: exchange vs local time, bytes over xGMI, rate per link
         x_ms, x_bytes = xstat["exchange_ms"] / 2, xstat["bytes_off_rank"] / 2
-        exchange_info = {"strategy": strategy, "chunks": n_chunks if strategy == "partition" else 1,
-                         "impl": ("C ABI (exchange.hip, RCCL on the ctx stream, no torch on the data path): sqlrs_exchange_all_to_all for "
-                                  "single-chunk exchanges, sqlrs_exchange_begin / send_chunk / finish for the chunked fact rows"
-                                  if abi_x["h"] is not None else "torch.distributed"),
-                         "fused_filter_partition": bool(fused_exchange and strategy == "partition"),
-                         "step_ms_profiled": round(prof_step_ms, 3), "exchange_ms": round(x_ms, 3),
-                         "local_ms": round(prof_step_ms - x_ms, 3), "bytes_off_rank_per_step": int(x_bytes),
-                         "GBps_per_rank": round(x_bytes / max(x_ms, 1e-9) / 1e6, 1),
-                         "GBps_per_link": round(x_bytes / max(x_ms, 1e-9) / 1e6 / max(world - 1, 1), 1),
-                         "ranks": rank_info,
-                         "note": "rank 0, two profiled steps with a sync behind the exchange phase (filter + partition "
-                                 "kernels + collectives, chunk k's all-to-all overlapping chunk k+1's kernels); split "
-                                 "sizes travel over a gloo side group; xGMI link peak 153 GB/s"}
+        exchange_info = dict(exchange_base(),
+                             step_ms_profiled=round(prof_step_ms, 3), exchange_ms=round(x_ms, 3),
+                             local_ms=round(prof_step_ms - x_ms, 3), bytes_off_rank_per_step=int(x_bytes),
+                             GBps_per_rank=round(x_bytes / max(x_ms, 1e-9) / 1e6, 1),
+                             GBps_per_link=round(x_bytes / max(x_ms, 1e-9) / 1e6 / max(world - 1, 1), 1),
+                             note="rank 0, two profiled steps with a sync behind the exchange phase (filter + partition "
+                                  "kernels + collectives, chunk k's all-to-all overlapping chunk k+1's kernels); split "
+                                  "sizes travel over a gloo side group; xGMI link peak 153 GB/s")
         # the other strategies, timed with the same wall clock over fewer steps (never the headline value)
         main_strategy = strategy
         for slot, alt in zip(("alternative", "alternative2"), [x for x in ("partition", "broadcast", "combine") if x != main_strategy]):
@@ -847,55 +995,8 @@ def main():
         cpu = cpu_baseline(args, abi, datagen, n_dim_total)
 
     if rank == 0:
-        line = {
-            "metric": "Mrows/sec for filter->hash-join->group-by pipeline; achieved HBM GB/s vs peak",
-            "value": round(value, 1), "unit": "Mrows/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "int64 keys / f64 sum", "data": "synthetic",
-            "config": {"workload": "C5 filter(val>0.5) -> hash-join(fact x dim on int64 key) -> group-by(key) COUNT,SUM(f64)",
-                       "fact_rows": n_fact_total, "dim_rows": n_dim_total, "groups": int(ngroups),
-                       "selectivity": round(got_rows / n_fact_total, 4),
-                       "operators": "Filter -> HashJoin -> HashAgg (3 operators)" if args.unfused else
-                       "Filter -> HashJoinAgg (HashAgg fused over the Inner HashJoin)" if args.separate_filter else
-                       "HashJoinAgg with the probe-side Filter handed to it (sqlrs_join_agg_set_probe_filter): "
-                       f"filter evaluated inside the first partition pass = {bool(pipe.filter_fused_batches)}",
-                       "parallelism": ("single GPU" if not multi else
-                                       f"x{world}: all-gather dim, local partial aggregation, all-to-all of partial aggregates, merge"
-                                       if strategy == "broadcast" else
-                                       f"x{world}: partitioned hash join, partial aggregation below the exchange — dim hash-partitioned on the "
-                                       "join key + RCCL all-to-all; HashAgg(Filter(fact slice)) by key on every rank; partial aggregates "
-                                       "hash-partitioned + RCCL all-to-all; HashJoinAgg(dim partition, partials) on the owning rank"
-                                       if strategy == "combine" else
-                                       f"x{world}: partitioned hash join — Filter below the exchange, fact + dim hash-partitioned on "
-                                       f"the join key, RCCL all-to-all in {n_chunks} overlapped chunks, local HashJoinAgg"
-                                       + ("; Filter + partition fused in one pass (sqlrs_hash_partition_filter)" if fused_exchange else ""))},
-            "roofline": roofline, "cpu_baseline": cpu,
-            # probe batches of the last step that took the library's fused join + aggregate route / had the Filter
-            # evaluated inside the first partition pass (0 = the operators were composed: the 2.5x slower form)
-            "fused_batches": int(pipe.fused_batches), "filter_fused_batches": int(pipe.filter_fused_batches),
-        }
-        if step_times:
-            line["ms_per_step_median"] = step_times["median"]
-            line["ms_per_step_each"] = step_times
-        if processes:
-            line["ms_per_step_processes"] = processes
-        if operators:
-            line["operators"] = operators
-        if variants:
-            line["c5_variants"] = variants
-        if exchange_info:
-            line["exchange"] = exchange_info
-        if json_fd is not None:
-            sys.stdout.flush()
-            os.write(json_fd, (json.dumps(line) + "\n").encode())
-        else:
-            print(json.dumps(line), flush=True)
-    if multi:
-        if abi_x["h"] is not None:
-            for old in abi_x["keep"]:
-                old.release()
-            be.fn("exchange_destroy")(abi_x["h"])
-        dist.destroy_process_group()
+        emit_line(roofline, cpu, step_times, processes, operators, variants, exchange_info)
+    teardown()
 
 
 def measure_in_fresh_processes(args, own_ms):

@@ -28,7 +28,7 @@ def test_bench_two_ranks_on_one_gpu(exchange, launcher, fused):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--rows", "6e6", "--dim-rows", "2e5",
-            "--exchange", exchange, "--no-cpu-baseline"]
+            "--exchange", exchange, "--no-cpu-baseline", "--full"]
     if launcher == "self":
         cmd = [sys.executable] + args
     else:
@@ -62,7 +62,7 @@ def test_bench_exchange_path_over_rccl_world_1(fused, impl):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "SQLRS_BENCH_SINGLE_DEVICE"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-exchange", "--steps", "3", "--warmup", "1",
-           "--rows", "2e7", "--dim-rows", "1e6", "--exchange", strategy, "--exchange-impl", impl, "--no-cpu-baseline"]
+           "--rows", "2e7", "--dim-rows", "1e6", "--exchange", strategy, "--exchange-impl", impl, "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -1,9 +1,9 @@
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 for c in FETCH_SIZE WRITE_SIZE; do
-rm -rf /tmp/pc3
-timeout 900 rocprofv3 --pmc $c --output-format csv -d /tmp/pc3 -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --operators > /dev/null 2>&1 < /dev/null
-f=$(find /tmp/pc3 -name '*counter_collection.csv' | head -1)
+d=$(mktemp -d)
+timeout 900 rocprofv3 --pmc $c --output-format csv -d "$d" -- python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --operators > /dev/null 2>&1 < /dev/null
+f=$(find "$d" -name '*counter_collection.csv' | head -1)
 python - "$f" $c <<'PY'
 import csv, sys, collections
 acc = collections.defaultdict(list)
