@@ -594,6 +594,45 @@ int sqlrs_hash_partition_filter(sqlrs_ctx_t *ctx, const sqlrs_batch_t *in, const
  *       any other DEVICE batch is copied once;
  *   sqlrs_exchange_plan        the receive side's bookkeeping as plain host arithmetic (no device): send_rows_all[q * world
  *       + p] = rows rank q sends to rank p -> rows / start offsets this rank receives per source rank. */
+/* Range partitioning for a multi-GPU ORDER BY (a sample sort over the exchange above; no reference analogue, the
+ * reference sorts in one process [ref: src/executor/order.rs:27-66]).  For a table T cut into W slices held by ranks
+ * 0 .. W-1 in this order, with row_base = the rows on lower ranks:
+ *   1. every rank samples its slice (sqlrs_range_sample), the tuples are all-gathered (any transport);
+ *   2. every rank computes the same W - 1 splitters from all tuples (sqlrs_range_splitters, host arithmetic);
+ *   3. every rank range-partitions its slice (sqlrs_range_partition) and sends part p to rank p
+ *      (sqlrs_exchange_all_to_all: received in source-rank order);
+ *   4. every rank runs sqlrs_order_* (the same ORDER BY list) over what it received.
+ * The rank outputs concatenated in rank order are bit-identical to sqlrs_order over T, ties included.  No call here is a
+ * collective.  ORDER BY keys: any list sqlrs_order_create accepts whose keys evaluate to Int32 / Int64 / Float64 /
+ * Boolean (a Utf8 key is refused with SQLRS_ERR_INTERNAL); payload columns may be of any type.
+ * TUPLE LAYOUT (sqlrs_range_tuple_words(K) = 2 K + 1 uint64 words, compared as unsigned integers word by word): per key,
+ * in ORDER BY order, a validity word (0 = NULL, 1 = valid) and the key encoded as the Order sorts it (0 for NULL; Int64:
+ * value ^ 2^63, Int32: widened to Int64 first, Float64: IEEE total order (bits ^ 2^63 when the sign is clear, ~bits when
+ * it is set: -0.0 < +0.0, NaNs outside the infinities), Boolean: 0 / 1; all of it complemented when asc = 0), then the
+ * row's global position row_base + i.  NULLs come first whatever the direction, equal keys in position order.
+ *   sqlrs_range_sample      min(num_samples, rows) tuples of the rows i * rows / min(num_samples, rows) (evenly spaced,
+ *       deterministic, in row order) into `tuples` (host, num_samples * words); *written = their number;
+ *   sqlrs_range_splitters   host arithmetic only (no ctx, no device, like sqlrs_exchange_plan): sorts the num_tuples
+ *       gathered tuples and writes num_parts - 1 splitters (splitter j - 1 = the (j * num_tuples / num_parts)-th smallest
+ *       tuple, counting from 0; nondecreasing) to `splitters` (host); with no tuples every splitter is the all-ones
+ *       tuple, so every row goes to part 0.  Returns SQLRS_ERR_INTERNAL on bad arguments (num_parts outside [1, 256],
+ *       NULL pointers);
+ *   sqlrs_range_partition   stable range partition: the part of a row = the number of splitters <= its tuple; the
+ *       output batch holds the input rows permuted so that part p = rows [offsets[p], offsets[p+1]) (`offsets`: host,
+ *       num_parts + 1 entries), input order kept inside a part.  `splitters`: host, num_parts - 1 tuples, nondecreasing
+ *       (checked; may be NULL when num_parts = 1).  One Int64 / Float64 key column without NULLs among <= 3 8-byte
+ *       columns without NULLs (>= 65536 rows, num_parts > 1) runs as one histogram + one scatter pass that read and
+ *       write every column once; other shapes sort part ids and gather every column.
+ *       (All three: SQLRS_ERR_INTERNAL with sqlrs_last_error set for a Utf8 key, num_parts outside [1, 256],
+ *       splitters that are not nondecreasing, NULL splitters with num_parts > 1.) */
+int sqlrs_range_tuple_words(int num_keys); /* -1 when num_keys < 1 */
+int sqlrs_range_sample(sqlrs_ctx_t *ctx, const sqlrs_batch_t *in, int num_keys, const sqlrs_order_by_t *order_by,
+                       int64_t row_base, int num_samples, uint64_t *tuples, int *written);
+int sqlrs_range_splitters(int num_keys, int64_t num_tuples, const uint64_t *tuples, int num_parts, uint64_t *splitters);
+int sqlrs_range_partition(sqlrs_ctx_t *ctx, const sqlrs_batch_t *in, int num_keys, const sqlrs_order_by_t *order_by,
+                          int64_t row_base, int num_parts, const uint64_t *splitters, int out_mem,
+                          sqlrs_batch_t **out, int64_t *offsets);
+
 #define SQLRS_EXCHANGE_ID_BYTES 128
 typedef struct sqlrs_exchange sqlrs_exchange_t;
 int sqlrs_exchange_unique_id(sqlrs_ctx_t *ctx, void *id_out);

@@ -399,6 +399,11 @@ class Backend:
             "exchange_destroy": (None, [vp]),
             "hash_partition": (i, [vp, pb, pe, i, i, ppb, C.POINTER(C.c_int64)]),
             "hash_partition_filter": (i, [vp, pb, pe, pe, i, i, ppb, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+            "range_tuple_words": (i, [i]),
+            "range_sample": (i, [vp, pb, i, C.POINTER(OrderBy), C.c_int64, i, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+            "range_splitters": (i, [i, C.c_int64, C.POINTER(C.c_uint64), i, C.POINTER(C.c_uint64)]),
+            "range_partition": (i, [vp, pb, i, C.POINTER(OrderBy), C.c_int64, i, C.POINTER(C.c_uint64), i, ppb,
+                                    C.POINTER(C.c_int64)]),
             "join_agg_create": (i, [vp, i, pe, pe, i, i, C.POINTER(C.c_int32), i, pe, i, C.POINTER(AggFunc), pvp]),
             "join_agg_build_push": (i, [vp, pb]),
             "join_agg_build_finish": (i, [vp]),
@@ -513,6 +518,57 @@ class Backend:
                                                     C.byref(pred.abi) if pred is not None else None, num_parts,
                                                     out_mem, C.byref(out), starts, rows))
         return self.wrap(out), list(starts), list(rows)
+
+    # ---- range partitioning (the multi-GPU ORDER BY: sample -> splitters -> partition -> exchange -> local Order)
+    @staticmethod
+    def _order_by_array(order_by):
+        """[expr.OrderBy] -> (C array of OrderBy, keep-alive of the packed expressions)"""
+        keep = [ob.expr.pack() for ob in order_by]
+        arr = (OrderBy * max(len(order_by), 1))(*[OrderBy(p.abi, int(ob.asc), 0) for p, ob in zip(keep, order_by)])
+        return arr, keep
+
+    def range_tuple_words(self, num_keys: int) -> int:
+        return self.fn("range_tuple_words")(num_keys)
+
+    def range_sample(self, batch, order_by, row_base: int, num_samples: int):
+        """-> uint64 array (written, tuple words): the tuples of evenly spaced rows (sqlrs_range_sample)"""
+        import numpy as np
+        b = as_batch(batch)
+        arr, _keep = self._order_by_array(order_by)
+        tw = 2 * len(order_by) + 1
+        out = np.zeros((max(num_samples, 1), tw), dtype=np.uint64)
+        written = C.c_int()
+        self.check(self.fn("range_sample")(self.ctx, b.ptr, len(order_by), arr, int(row_base), int(num_samples),
+                                           out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(written)))
+        return out[:written.value].copy()
+
+    def range_splitters(self, num_keys: int, tuples, num_parts: int):
+        """host arithmetic (sqlrs_range_splitters): gathered tuples (rows of 2 K + 1 words) -> (num_parts - 1, words)"""
+        import numpy as np
+        tw = 2 * num_keys + 1
+        t = np.ascontiguousarray(np.asarray(tuples, dtype=np.uint64).reshape(-1, tw))
+        out = np.zeros((max(num_parts - 1, 1), tw), dtype=np.uint64)
+        st = self.fn("range_splitters")(num_keys, len(t), t.ctypes.data_as(C.POINTER(C.c_uint64)), num_parts,
+                                        out.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if st != OK:
+            raise ExecutorError(st, "range_splitters: bad arguments")
+        return out[:num_parts - 1].copy()
+
+    def range_partition(self, batch, order_by, row_base: int, num_parts: int, splitters, out_mem: int = MEM_DEVICE):
+        """-> (LibBatch permuted by range part, offsets list of num_parts + 1 ints) (sqlrs_range_partition);
+        `splitters`: (num_parts - 1, words) uint64 array, or None"""
+        import numpy as np
+        b = as_batch(batch)
+        arr, _keep = self._order_by_array(order_by)
+        sp = None
+        if splitters is not None:
+            spa = np.ascontiguousarray(np.asarray(splitters, dtype=np.uint64))
+            sp = spa.ctypes.data_as(C.POINTER(C.c_uint64))
+        out = C.POINTER(Batch)()
+        offs = (C.c_int64 * (num_parts + 1))()
+        self.check(self.fn("range_partition")(self.ctx, b.ptr, len(order_by), arr, int(row_base), num_parts, sp, out_mem,
+                                              C.byref(out), offs))
+        return self.wrap(out), list(offs)
 
     # ---- exchange (RCCL all-to-all of hash partitions behind the C ABI; one process per GPU)
     EXCHANGE_ID_BYTES = 128

@@ -6,7 +6,7 @@
 //    source once: ~G x the column's bytes are fetched);
 //  * fast path (up to three 8-byte columns without NULLs — partial aggregates (key, count, sum),
 //    filtered fact rows (key, val)): a stable LDS-staged multi-split that carries the columns
-//    (split_hist / split_scatter below): every column is read once and written once
+//    (split_hist / split_scatter, split_kernels.hpp): every column is read once and written once
 //    (1e7 x 3 columns: 0.54 -> 0.2 ms).
 //  * fused path (sqlrs_hash_partition_filter): Filter + compaction + partition in ONE pass.  A counting
 //    multi-split needs every (tile, partition) count before the first row moves, and a FilterExecutor below
@@ -19,13 +19,9 @@
 #include "device_utils.hpp"
 #include "prims.hpp"
 #include "radix_part.hpp"
+#include "split_kernels.hpp"
 
 namespace sq {
-
-__device__ __forceinline__ uint32_t part_of(uint64_t key, uint32_t parts) {
-  uint64_t h = mix64(key ^ 0x5851f42d4c957f2dULL);
-  return (uint32_t)(((h >> 32) * (uint64_t)parts) >> 32);
-}
 
 __global__ __launch_bounds__(BLOCK) void part_ids_kernel(const uint64_t *__restrict__ keys,
                                                          const uint64_t *__restrict__ validity,
@@ -45,126 +41,7 @@ __global__ __launch_bounds__(BLOCK) void part_ids_kernel(const uint64_t *__restr
   if (threadIdx.x < parts && h[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)h[threadIdx.x]);
 }
 
-// ---- fast path: stable multi-split of NC 8-byte columns by the partition of column `kc` ----
-constexpr int SP_WG = 512, SP_WAVES = 8, SP_ITEMS = 8, SP_TILE = SP_WG * SP_ITEMS;
-
-__global__ __launch_bounds__(SP_WG) void split_hist_kernel(const uint64_t *__restrict__ keys, int64_t n,
-                                                           uint32_t parts, int64_t ntiles,
-                                                           uint32_t *__restrict__ hist) {
-  __shared__ uint32_t h[256];
-  if (threadIdx.x < 256) h[threadIdx.x] = 0;
-  const int64_t base = (int64_t)blockIdx.x * SP_TILE + threadIdx.x;
-  uint64_t k[SP_ITEMS];
-#pragma unroll
-  for (int r = 0; r < SP_ITEMS; r++) k[r] = keys[min(base + r * SP_WG, n - 1)];
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < SP_ITEMS; r++)
-    if (base + r * SP_WG < n) atomicAdd(&h[part_of(k[r], parts)], 1u);
-  __syncthreads();
-  if (threadIdx.x < parts) hist[(int64_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
-}
-
-// Same scheme as the radix sort's stable scatter (sort.hip): row order inside the tile is (wave,
-// chunk, lane); lanes of a chunk with the same partition find each other with 8 ballots, the first
-// of them bumps the wave's own counter, a prefix over waves and partitions gives the tile-local
-// position, the tile is staged partition-major in LDS and leaves as one run per partition.
-template <int NC>
-__global__ __launch_bounds__(SP_WG) void split_scatter_kernel(
-    const uint64_t *__restrict__ c0, const uint64_t *__restrict__ c1, const uint64_t *__restrict__ c2, int kc,
-    int64_t n, uint32_t parts, int64_t ntiles, const uint32_t *__restrict__ offsets, uint64_t *__restrict__ o0,
-    uint64_t *__restrict__ o1, uint64_t *__restrict__ o2) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char sp_smem[];
-  uint64_t *s0 = (uint64_t *)sp_smem;
-  uint64_t *s1 = s0 + SP_TILE;
-  uint64_t *s2 = s1 + (NC >= 2 ? SP_TILE : 0);
-  uint8_t *spart = (uint8_t *)(s2 + (NC >= 3 ? SP_TILE : 0));
-  __shared__ uint32_t wcnt[SP_WAVES][256];
-  __shared__ uint32_t dstart[256];
-  __shared__ int64_t gbase[256];
-  __shared__ uint32_t s_wsum[4];
-  const int w = wave_id(), lane = lane_id();
-  const int64_t tbase = (int64_t)blockIdx.x * SP_TILE;
-  const int64_t wrow = tbase + (int64_t)w * (SP_ITEMS * 64) + lane;
-  uint64_t a[SP_ITEMS], b[NC >= 2 ? SP_ITEMS : 1], c[NC >= 3 ? SP_ITEMS : 1];
-#pragma unroll
-  for (int j = 0; j < SP_ITEMS; j++) {
-    const int64_t i = min(wrow + j * 64, n - 1);
-    a[j] = c0[i];
-    if (NC >= 2) b[j] = c1[i];
-    if (NC >= 3) c[j] = c2[i];
-  }
-  uint32_t goff = threadIdx.x < parts ? offsets[(int64_t)threadIdx.x * ntiles + blockIdx.x] : 0;
-#pragma unroll
-  for (int q = 0; q < 4; q++) wcnt[w][lane + 64 * q] = 0;
-  uint32_t rnk[SP_ITEMS], prt[SP_ITEMS];
-#pragma unroll
-  for (int j = 0; j < SP_ITEMS; j++) {
-    const bool valid = wrow + j * 64 < n;
-    const uint64_t key = kc == 0 ? a[j] : (kc == 1 ? b[NC >= 2 ? j : 0] : c[NC >= 3 ? j : 0]);
-    const uint32_t d = part_of(key, parts);
-    prt[j] = d;
-    uint64_t peers = __ballot(valid);
-#pragma unroll
-    for (int bit = 0; bit < 8; bit++) {
-      const bool on = (d >> bit) & 1;
-      const uint64_t bm = __ballot(on);
-      peers &= on ? bm : ~bm;
-    }
-    const uint32_t r = (uint32_t)mbcnt(peers);
-    uint32_t old = 0;
-    if (valid && r == 0) {
-      old = wcnt[w][d];
-      wcnt[w][d] = old + (uint32_t)__popcll(peers);
-    }
-    old = (uint32_t)__shfl((int)old, valid ? __builtin_ctzll(peers) : 0, 64);
-    rnk[j] = old + r;
-  }
-  __syncthreads();
-  if (threadIdx.x < 256) {
-    uint32_t acc = 0;
-#pragma unroll
-    for (int q = 0; q < SP_WAVES; q++) {
-      uint32_t cnt = wcnt[q][threadIdx.x];
-      wcnt[q][threadIdx.x] = acc;
-      acc += cnt;
-    }
-    uint32_t inc = wave_iscan_u32(acc);
-    if (lane == 63) s_wsum[w] = inc;
-    dstart[threadIdx.x] = inc - acc;
-  }
-  __syncthreads();
-  if (threadIdx.x < 256) {
-    uint32_t wb = 0;
-    for (int q = 0; q < w; q++) wb += s_wsum[q];
-    uint32_t ds = dstart[threadIdx.x] + wb;
-    dstart[threadIdx.x] = ds;
-    gbase[threadIdx.x] = (int64_t)goff - (int64_t)ds;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < SP_ITEMS; j++) {
-    if (wrow + j * 64 >= n) continue;
-    const uint32_t d = prt[j];
-    const uint32_t p = dstart[d] + wcnt[w][d] + rnk[j];
-    s0[p] = a[j];
-    if (NC >= 2) s1[p] = b[j];
-    if (NC >= 3) s2[p] = c[j];
-    spart[p] = (uint8_t)d;
-  }
-  __syncthreads();
-  const uint32_t len = (uint32_t)min<int64_t>(SP_TILE, n - tbase);
-#pragma unroll
-  for (int j = 0; j < SP_ITEMS; j++) {
-    const uint32_t p = j * SP_WG + threadIdx.x;
-    if (p < len) {
-      const int64_t g = gbase[spart[p]] + p;
-      o0[g] = s0[p];
-      if (NC >= 2) o1[g] = s1[p];
-      if (NC >= 3) o2[g] = s2[p];
-    }
-  }
-}
+// ---- fast path: the stable multi-split of split_kernels.hpp with HashPart ----
 
 // One-pass Filter + partition (see the header of this file).  Same in-tile ranking and LDS staging as
 // split_scatter_kernel; the (tile, partition) run start comes from an atomic claim on the partition's fill
@@ -310,8 +187,9 @@ extern "C" int sqlrs_hash_partition(sqlrs_ctx_t *ctx, const sqlrs_batch_t *in, c
         const int64_t ntiles = ceil_div(n, SP_TILE);
         BufP hist = ctx->alloc(4 * (size_t)(num_parts * ntiles)), offs = ctx->alloc(4 * (size_t)(num_parts * ntiles));
         BufP total = ctx->alloc(8);
+        const HashPart pf{(uint32_t)num_parts};
         split_hist_kernel<<<dim3((unsigned)ntiles), dim3(SP_WG), 0, ctx->stream>>>(
-            ib.col(kcol).v<uint64_t>(), n, (uint32_t)num_parts, ntiles, hist->as<uint32_t>());
+            ib.col(kcol).v<uint64_t>(), n, pf, ntiles, hist->as<uint32_t>());
         exclusive_scan_u32(ctx, hist->as<uint32_t>(), (int64_t)num_parts * ntiles, nullptr, offs->as<uint32_t>(),
                            total->as<uint64_t>());
         DBatch o;
@@ -333,10 +211,10 @@ extern "C" int sqlrs_hash_partition(sqlrs_ctx_t *ctx, const sqlrs_batch_t *in, c
         dim3 g((unsigned)ntiles), b(SP_WG);
 #define SQ_SPLIT(NC)                                                                                          \
   do {                                                                                                        \
-    auto kfn = split_scatter_kernel<NC>;                                                                      \
+    auto kfn = split_scatter_kernel<HashPart, NC>;                                                            \
     allow_big_lds(ctx, kfn, 112 * 1024); /* (this kernel also has ~40 KiB of static LDS) */                   \
-    kfn<<<g, b, lds, ctx->stream>>>(inp[0], inp[1], inp[2], kcol, n, (uint32_t)num_parts, ntiles,             \
-                                    offs->as<uint32_t>(), outp[0], outp[1], outp[2]);                         \
+    kfn<<<g, b, lds, ctx->stream>>>(inp[0], inp[1], inp[2], kcol, n, pf, ntiles, offs->as<uint32_t>(),        \
+                                    outp[0], outp[1], outp[2], nullptr);                                      \
   } while (0)
         if (nc == 1) SQ_SPLIT(1); else if (nc == 2) SQ_SPLIT(2); else SQ_SPLIT(3);
 #undef SQ_SPLIT

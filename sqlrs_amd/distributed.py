@@ -52,6 +52,105 @@ def partition_numpy(columns: Sequence[np.ndarray], parts: int, valid: Optional[n
     return [c[order] for c in columns], offsets.tolist()
 
 
+# ---- range partitioning: the multi-GPU ORDER BY (a sample sort; range_partition.hip, include/sqlrs_hip.h) ----------
+_TOP = np.uint64(1 << 63)
+
+
+def ordered_key_np(values: np.ndarray) -> np.ndarray:
+    """the local Order's key image (ops.hip sort_key_kernel): int64 / int32 (widened) -> value ^ 2^63, float64 -> IEEE
+    total order, bool -> 0 / 1"""
+    v = np.asarray(values)
+    if v.dtype == np.bool_:
+        return v.astype(np.uint64)
+    if v.dtype == np.float64:
+        b = v.view(np.uint64)
+        return np.where((b >> np.uint64(63)) != 0, ~b, b | _TOP)
+    if v.dtype in (np.int64, np.int32):
+        return v.astype(np.int64).view(np.uint64) ^ _TOP
+    raise TypeError(f"unsupported ORDER BY key type {v.dtype}")
+
+
+def range_tuples_numpy(keys, row_base: int, rows: Optional[np.ndarray] = None) -> np.ndarray:
+    """Host restatement of the tuples of sqlrs_range_sample / _partition.  keys: [(values, valid or None, asc)] in ORDER
+    BY order; rows: the rows to encode (default: all, in order).  -> (len(rows), 2 K + 1) uint64: per key a validity word
+    and the encoded key (0 for NULL, complemented for DESC), then row_base + row."""
+    n = len(keys[0][0])
+    rows = np.arange(n, dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64)
+    out = np.zeros((len(rows), 2 * len(keys) + 1), dtype=np.uint64)
+    for k, (values, valid, asc) in enumerate(keys):
+        u = ordered_key_np(np.asarray(values)[rows])
+        if not asc:
+            u = ~u
+        ok = np.ones(len(rows), dtype=bool) if valid is None else np.asarray(valid, dtype=bool)[rows]
+        out[:, 2 * k] = ok.astype(np.uint64)
+        out[:, 2 * k + 1] = np.where(ok, u, np.uint64(0))
+    out[:, -1] = (rows + int(row_base)).astype(np.uint64)
+    return out
+
+
+def range_sample_rows(n: int, num_samples: int) -> np.ndarray:
+    """the rows sqlrs_range_sample encodes: i * n // m for i < m = min(num_samples, n)"""
+    m = min(int(num_samples), int(n))
+    return np.arange(m, dtype=np.int64) * n // max(m, 1)
+
+
+def _lex_le(s: np.ndarray, t: np.ndarray) -> np.ndarray:
+    """splitter tuple s <= every row of t (unsigned, word by word) as a bool vector"""
+    le = np.ones(len(t), dtype=bool)
+    for w in range(t.shape[1] - 1, -1, -1):
+        le = (s[w] < t[:, w]) | ((s[w] == t[:, w]) & le)
+    return le
+
+
+def range_splitters_numpy(tuples: np.ndarray, parts: int) -> np.ndarray:
+    """sqlrs_range_splitters: splitter j - 1 = the (j * T // parts)-th smallest of the T tuples; all-ones without tuples"""
+    t = np.asarray(tuples, dtype=np.uint64)
+    tw = t.shape[1]
+    if len(t) == 0:
+        return np.full((parts - 1, tw), np.uint64((1 << 64) - 1), dtype=np.uint64)
+    srt = t[np.lexsort(t.T[::-1])]
+    return np.stack([srt[j * len(t) // parts] for j in range(1, parts)]) if parts > 1 else np.zeros((0, tw), np.uint64)
+
+
+def range_partition_numpy(columns: Sequence[np.ndarray], tuples: np.ndarray, splitters: np.ndarray):
+    """Host restatement of sqlrs_range_partition: part of a row = number of splitters <= its tuple; rows permuted so that
+    part p is contiguous (input order kept inside a part) + the parts + 1 offsets"""
+    parts = len(splitters) + 1
+    p = np.zeros(len(tuples), dtype=np.int64)
+    for s in splitters:
+        p += _lex_le(s, tuples)
+    order = np.argsort(p, kind="stable")
+    counts = np.bincount(p, minlength=parts)
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return [c[order] for c in columns], offsets.tolist()
+
+
+def distributed_order(num_rows: int, world: int, rank: int, *, allgather, sample, partition, exchange, order,
+                      splitters=None, samples_per_rank: int = 1024):
+    """ORDER BY over W ranks (a sample sort); returns this rank's piece of the global result — the pieces in rank order
+    are the ORDER BY of the table the rank slices make in rank order, ties included.  No device, no transport of its own:
+
+        allgather(obj) -> [obj of rank 0, 1, ...]                (host objects: ints, uint64 arrays)
+        sample(row_base, num_samples) -> (m, 2 K + 1) uint64     (sqlrs_range_sample / range_tuples_numpy)
+        splitters(tuples, world) -> (world - 1, 2 K + 1) uint64  (sqlrs_range_splitters; default range_splitters_numpy)
+        partition(row_base, splitters) -> (parts, offsets)       (sqlrs_range_partition / range_partition_numpy)
+        exchange(parts, offsets) -> what this rank received, in source-rank order (sqlrs_exchange_all_to_all / gloo)
+        order(received) -> the sorted piece                      (sqlrs_order_* / the oracle's Order)
+
+    Every rank samples in proportion to its share of the rows (samples_per_rank * world in all), so uneven slices do not
+    skew the splitters."""
+    counts = [int(c) for c in allgather(int(num_rows))]
+    row_base, total = sum(counts[:rank]), sum(counts)
+    want = 0 if total == 0 else -(-samples_per_rank * world * int(num_rows) // total)
+    mine = np.asarray(sample(row_base, want), dtype=np.uint64)
+    gathered = [np.asarray(t, dtype=np.uint64) for t in allgather(mine)]
+    tw = mine.shape[1]
+    tuples = np.concatenate([g.reshape(-1, tw) for g in gathered])
+    spl = (splitters or range_splitters_numpy)(tuples, world)
+    parts, offsets = partition(row_base, spl)
+    return order(exchange(parts, offsets))
+
+
 def partition_filter_numpy(columns: Sequence[np.ndarray], parts: int, keep: Optional[np.ndarray] = None):
     """Host restatement of sqlrs_hash_partition_filter's output layout on column 0: every partition owns a
     region of ``cap`` = len rows (rounded up to 64), filled from its start with the kept rows of that
