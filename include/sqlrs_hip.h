@@ -632,6 +632,44 @@ int sqlrs_range_splitters(int num_keys, int64_t num_tuples, const uint64_t *tupl
 int sqlrs_range_partition(sqlrs_ctx_t *ctx, const sqlrs_batch_t *in, int num_keys, const sqlrs_order_by_t *order_by,
                           int64_t row_base, int num_parts, const uint64_t *splitters, int out_mem,
                           sqlrs_batch_t **out, int64_t *offsets);
+/* ORDER BY ... LIMIT k over the same W ranks (a distributed selection by tuple bound; the reference's
+ * PhysicalLimit(PhysicalOrder) [ref: src/executor/limit.rs:12-80 over src/executor/order.rs:27-66]).  Only the rows that can
+ * still be among the global first k travel, to ONE root rank:
+ *   1. all-gather the row counts (row_base, N); every rank samples its slice (sqlrs_range_sample, in proportion to its
+ *      share) and the tuples are all-gathered;
+ *   2. every rank computes the same bound tuple B from the samples, N, k = offset + limit and an attempt number a
+ *      (sqlrs_range_bound, host arithmetic);
+ *   3. every rank keeps its rows whose tuple is strictly below B, in input order (sqlrs_range_select) and all-gathers how
+ *      many it kept; below min(k, N) in all, every rank repeats 2-3 with a + 1 (the counts are the same everywhere, so all
+ *      ranks agree; the last attempt's bound is the all-ones tuple, which keeps every row);
+ *   4. the candidates go to the root (sqlrs_exchange_all_to_all, part_rows = the candidates for the root, 0 for every other
+ *      rank: received in source-rank order), which runs sqlrs_order_* with sqlrs_order_set_limit(k); its first min(k, N)
+ *      rows are the first min(k, N) rows of sqlrs_order over the whole table, ties included; the caller applies OFFSET /
+ *      LIMIT to them.  Every other rank's result is empty.
+ * Why: at least k tuples lie below B and the first k rows are the k smallest tuples, so the candidates are a superset of
+ * them; inside a rank the candidates keep input order and they arrive in rank order, i.e. in global position order, so
+ * the stable Order breaks ties exactly as the global one; and because the position is part of the tuple, a run of equal
+ * keys is cut at a position instead of being sent whole.
+ *   sqlrs_range_bound       host arithmetic only (no ctx, no device): k <= 0 -> the all-zero tuple (keeps nothing);
+ *       k >= total_rows, no tuples, or j past the last tuple -> the all-ones tuple (keeps every row); otherwise the j-th
+ *       smallest of the num_tuples gathered tuples, counting from 0, with
+ *           j = (c + ceil(2 sqrt(c)) + 2) * 4^attempt - 1,   c = ceil(k * num_tuples / total_rows)
+ *       (nondecreasing in attempt; all-ones once 4^attempt > num_tuples).  The slack grows with sqrt(c), the deviation of
+ *       the number of rows below a sample quantile: random keys need a second attempt in <= 2.5 % of the cases for
+ *       k = 1e3 .. 1e6 of 1e7 rows with 8192 samples, against 6 - 49 % for a constant slack of 2.
+ *       SQLRS_ERR_INTERNAL on bad arguments (num_keys < 1, num_tuples < 0, total_rows < 0, attempt < 0, NULL pointers);
+ *   sqlrs_range_select      the rows of `in` whose tuple (row_base + i as position) is strictly below `bound` (host, one
+ *       tuple of sqlrs_range_tuple_words(num_keys) words), in input order, every column carried (any type, NULLs
+ *       included).  Keys as sqlrs_range_partition (a Utf8 key: SQLRS_ERR_INTERNAL naming Utf8, nothing queued); row_base
+ *       < 0 and NULL pointers are errors.  No tuple is written: one kernel reads each key column once, encodes it on the fly
+ *       and leaves one selection bit per row, then the kept rows' ids (one count fetch) and one gather per column.  More than
+ *       16 keys: the tuples are written and compared instead.  Measured on one MI355X (tools/range_topk_bench.py): 0.248 ms
+ *       for 1e8 rows of (int64 key, f64) keeping 6 897 of them, against 0.84 ms for sqlrs_range_partition into 8 parts
+ *       (DESIGN.md §4.6).  No top-k exchange has run on more than one GPU. */
+int sqlrs_range_bound(int num_keys, int64_t num_tuples, const uint64_t *tuples, int64_t total_rows, int64_t k, int attempt,
+                      uint64_t *bound);
+int sqlrs_range_select(sqlrs_ctx_t *ctx, const sqlrs_batch_t *in, int num_keys, const sqlrs_order_by_t *order_by,
+                       int64_t row_base, const uint64_t *bound, int out_mem, sqlrs_batch_t **out);
 
 #define SQLRS_EXCHANGE_ID_BYTES 128
 typedef struct sqlrs_exchange sqlrs_exchange_t;

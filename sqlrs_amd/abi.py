@@ -404,6 +404,8 @@ class Backend:
             "range_splitters": (i, [i, C.c_int64, C.POINTER(C.c_uint64), i, C.POINTER(C.c_uint64)]),
             "range_partition": (i, [vp, pb, i, C.POINTER(OrderBy), C.c_int64, i, C.POINTER(C.c_uint64), i, ppb,
                                     C.POINTER(C.c_int64)]),
+            "range_bound": (i, [i, C.c_int64, C.POINTER(C.c_uint64), C.c_int64, C.c_int64, i, C.POINTER(C.c_uint64)]),
+            "range_select": (i, [vp, pb, i, C.POINTER(OrderBy), C.c_int64, C.POINTER(C.c_uint64), i, ppb]),
             "join_agg_create": (i, [vp, i, pe, pe, i, i, C.POINTER(C.c_int32), i, pe, i, C.POINTER(AggFunc), pvp]),
             "join_agg_build_push": (i, [vp, pb]),
             "join_agg_build_finish": (i, [vp]),
@@ -569,6 +571,31 @@ class Backend:
         self.check(self.fn("range_partition")(self.ctx, b.ptr, len(order_by), arr, int(row_base), num_parts, sp, out_mem,
                                               C.byref(out), offs))
         return self.wrap(out), list(offs)
+
+    def range_bound(self, num_keys: int, tuples, total_rows: int, k: int, attempt: int):
+        """host arithmetic (sqlrs_range_bound): gathered tuples (rows of 2 K + 1 words) -> the bound tuple of `attempt`
+        for the first k of total_rows rows (uint64 array of 2 K + 1 words)"""
+        import numpy as np
+        tw = 2 * num_keys + 1
+        t = np.ascontiguousarray(np.asarray(tuples, dtype=np.uint64).reshape(-1, tw))
+        out = np.zeros(tw, dtype=np.uint64)
+        st = self.fn("range_bound")(num_keys, len(t), t.ctypes.data_as(C.POINTER(C.c_uint64)), int(total_rows), int(k),
+                                    int(attempt), out.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if st != OK:
+            raise ExecutorError(st, "range_bound: bad arguments")
+        return out
+
+    def range_select(self, batch, order_by, row_base: int, bound, out_mem: int = MEM_DEVICE):
+        """-> LibBatch of the rows whose tuple is strictly below `bound` (2 K + 1 uint64 words), in input order
+        (sqlrs_range_select)"""
+        import numpy as np
+        b = as_batch(batch)
+        arr, _keep = self._order_by_array(order_by)
+        bd = np.ascontiguousarray(np.asarray(bound, dtype=np.uint64).reshape(-1))
+        out = C.POINTER(Batch)()
+        self.check(self.fn("range_select")(self.ctx, b.ptr, len(order_by), arr, int(row_base),
+                                           bd.ctypes.data_as(C.POINTER(C.c_uint64)), out_mem, C.byref(out)))
+        return self.wrap(out)
 
     # ---- exchange (RCCL all-to-all of hash partitions behind the C ABI; one process per GPU)
     EXCHANGE_ID_BYTES = 128

@@ -14,6 +14,7 @@ testable on CPU (``gloo``, world_size 2) and so that tests can check device and 
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -149,6 +150,87 @@ def distributed_order(num_rows: int, world: int, rank: int, *, allgather, sample
     spl = (splitters or range_splitters_numpy)(tuples, world)
     parts, offsets = partition(row_base, spl)
     return order(exchange(parts, offsets))
+
+
+# ---- ORDER BY ... LIMIT over ranks: only the rows that can be among the first k travel (include/sqlrs_hip.h) -------
+_ALL_ONES = np.uint64((1 << 64) - 1)
+
+
+def range_bound_index(num_tuples: int, total_rows: int, k: int, attempt: int) -> int:
+    """sqlrs_range_bound's j: (c + ceil(2 sqrt(c)) + 2) * 4^attempt - 1 with c = ceil(k T / N); -1 = past the last tuple"""
+    T, N = int(num_tuples), int(total_rows)
+    c = -(-int(k) * T // N)
+    if c >= T:
+        return -1
+    r = math.isqrt(4 * c - 1) + 1  # smallest r with r * r >= 4 c (c >= 1)
+    j1 = (c + r + 2) * 4 ** int(attempt)
+    return -1 if j1 > T else j1 - 1
+
+
+def range_bound_numpy(tuples: np.ndarray, total_rows: int, k: int, attempt: int) -> np.ndarray:
+    """sqlrs_range_bound: all zeros for k <= 0; all ones for k >= total_rows, no tuples or j past the end; else the j-th
+    smallest tuple (counting from 0)"""
+    t = np.asarray(tuples, dtype=np.uint64)
+    tw = t.shape[1]
+    if k <= 0:
+        return np.zeros(tw, dtype=np.uint64)
+    j = -1 if (k >= total_rows or len(t) == 0) else range_bound_index(len(t), total_rows, k, attempt)
+    if j < 0:
+        return np.full(tw, _ALL_ONES, dtype=np.uint64)
+    return t[np.lexsort(t.T[::-1])][j].copy()
+
+
+def _lex_lt_bound(t: np.ndarray, bound: np.ndarray) -> np.ndarray:
+    """every row tuple of t < bound (unsigned, word by word) as a bool vector"""
+    lt = np.zeros(len(t), dtype=bool)
+    for w in range(t.shape[1] - 1, -1, -1):
+        lt = (t[:, w] < bound[w]) | ((t[:, w] == bound[w]) & lt)
+    return lt
+
+
+def range_select_numpy(columns: Sequence[np.ndarray], tuples: np.ndarray, bound: np.ndarray):
+    """Host restatement of sqlrs_range_select: the rows whose tuple is strictly below `bound`, in input order"""
+    b = np.asarray(bound, dtype=np.uint64).reshape(-1)
+    keep = _lex_lt_bound(np.asarray(tuples, dtype=np.uint64).reshape(-1, len(b)), b)
+    return [c[keep] for c in columns]
+
+
+def distributed_topk(num_rows: int, world: int, rank: int, *, k: int, allgather, sample, select, bound=None,
+                     gather_to_root, order, root: int = 0, samples_per_rank: int = 1024):
+    """ORDER BY ... LIMIT over W ranks: the first min(k, N) rows of the ORDER BY of the table the rank slices make in rank
+    order, ties included, on `root`; the caller applies OFFSET / LIMIT (k = offset + limit).  No device, no transport of
+    its own:
+
+        allgather(obj) -> [obj of rank 0, 1, ...]                   (host objects: ints, uint64 arrays)
+        sample(row_base, num_samples) -> (m, 2 K + 1) uint64        (sqlrs_range_sample / range_tuples_numpy)
+        bound(tuples, total_rows, k, attempt) -> 2 K + 1 uint64     (sqlrs_range_bound; default range_bound_numpy)
+        select(row_base, bound) -> (candidates, their number)       (sqlrs_range_select / range_select_numpy)
+        gather_to_root(candidates, count) -> on root what every rank sent, in source-rank order; elsewhere anything
+                                                                    (sqlrs_exchange_all_to_all with part_rows = count
+                                                                    for the root, 0 for the others)
+        order(received, k) -> the sorted first k rows (or more)     (sqlrs_order_* with sqlrs_order_set_limit(k))
+
+    -> (result, info): result = order(..)'s output on the root (the caller keeps its first min(k, N) rows) and None on
+    every other rank; info = {"attempts": bounds tried - 1, "candidates": rows sent in all, "total_rows": N}.  Every
+    attempt whose candidates fall short of min(k, N) in all is repeated by every rank with the next attempt number."""
+    counts = [int(c) for c in allgather(int(num_rows))]
+    row_base, total = sum(counts[:rank]), sum(counts)
+    want = 0 if total == 0 else -(-samples_per_rank * world * int(num_rows) // total)
+    mine = np.asarray(sample(row_base, want), dtype=np.uint64)
+    tw = mine.shape[1]
+    tuples = np.concatenate([np.asarray(g, dtype=np.uint64).reshape(-1, tw) for g in allgather(mine)])
+    need = min(int(k), total)
+    attempt = 0
+    while True:
+        b = np.asarray((bound or range_bound_numpy)(tuples, total, int(k), attempt), dtype=np.uint64)
+        cand, kept = select(row_base, b)
+        got = sum(int(x) for x in allgather(int(kept)))
+        if got >= need or bool((b == _ALL_ONES).all()):
+            break
+        attempt += 1
+    received = gather_to_root(cand, int(kept))
+    info = {"attempts": attempt, "candidates": got, "total_rows": total}
+    return (order(received, int(k)) if rank == root else None), info
 
 
 def partition_filter_numpy(columns: Sequence[np.ndarray], parts: int, keep: Optional[np.ndarray] = None):
