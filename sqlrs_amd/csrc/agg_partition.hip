@@ -179,19 +179,14 @@ static double hll_pass(Ctx *ctx, const uint64_t *keys, const uint64_t *validity,
 double estimate_distinct(Ctx *ctx, const uint64_t *keys, const uint64_t *validity, int64_t n,
                          uint64_t *omin, uint64_t *omax, bool *sampled) {
   if (sampled) *sampled = false;
-  static const int opt_env = [] { // test / tuning hook: 0 = always the exact pass
-    const char *e = hook("SQLRS_SAMPLED_STATS");
-    return e ? std::atoi(e) : 1;
-  }();
   constexpr double SATURATED = 0.8; // half the sample holds >= this share of the sample's keys: every group has been seen
   // Between DISJOINT (ordered / clustered rows: a half holds half of the sample's keys) and SATURATED lie heavy-tailed keys —
   // Zipf(1.1) over 1e6 groups: the halves share the frequent keys and each has its own rare ones — where the sample is short
   // of the rare groups only: the estimate is scaled by the missing share instead of hashing every row (C4 Zipf: the exact pass
-  // cost 0.34 of 2.97 ms); SQLRS_STATS_DISJOINT (read per call) moves the line
-  double DISJOINT = 0.6;
-  if (const char *dj = hook("SQLRS_STATS_DISJOINT")) DISJOINT = std::atof(dj);
+  // cost 0.34 of 2.97 ms)
+  constexpr double DISJOINT = 0.6;
   double half = 0;
-  if (sampled && opt_env && !validity && n >= (1ll << 24)) {
+  if (sampled && !validity && n >= (1ll << 24)) {
     const int stride = 8;
     const double e = hll_pass(ctx, keys, validity, n, 0, omin, omax, stride, &half);
     if (e <= 0.2 * (double)(n / stride) && half >= DISJOINT * e) { // every group is seen several times in the sample (or only rare ones are missed): the estimate stands
@@ -1409,25 +1404,16 @@ bool partitioned_preaggregate(Ctx *ctx, const PartAggSpec &spec, const PartAggIn
   // (36 KiB tables, four workgroups per CU) that was ~5 trips per row instead of ~2:
   // 3.7 ms vs 3.0 ms for the C5 bucket pass.  Fewer groups per table would need more buckets,
   // which costs more in the partition passes than it saves here.
-  const char *lds_e = hook("SQLRS_LDS_AGG_KB"); // tuning hook, read per call
-  const size_t lds_budget = (size_t)(lds_e ? std::atoi(lds_e) : 72) * 1024;
+  constexpr size_t lds_budget = 72 * 1024;
   const size_t slot_bytes = 8 + 8 * (size_t)spec.n_acc + 4; // key, accumulators, first row
   uint32_t cap = 1;
   while ((size_t)(cap * 2 + 2) * slot_bytes <= lds_budget) cap *= 2;
-  static const double load_factor = [] { // tuning hook
-    const char *e = hook("SQLRS_LDS_LOAD");
-    return e ? std::atof(e) : 0.275;
-  }();
+  constexpr double load_factor = 0.275;
   const double groups_per_table = cap * load_factor;
   double want = est * 1.15 / groups_per_table;
-  static const double max_frac = [] { // tuning hook: largest groups / rows ratio taken by this route
-    const char *e = hook("SQLRS_PART_MAX_FRAC");
-    return e ? std::atof(e) : 1.0;
-  }();
   // (mostly distinct keys used to be sent to the row route, "est > n / 2": 17 ms instead of 1.7 ms
   // for 1e7 rows with 8e6 groups — the bucket count limit below is the only size limit now)
   if (!join_mode) est = std::min(est, (double)n);
-  if (!join_mode && est > max_frac * (double)n) return false;
   // Dense keys: when the keys of interest fill most of their range (surrogate keys, dimension
   // primary keys) the partition is by key range and the bucket tables are addressed directly:
   // R = 2^rbits slots of 8 * n_acc + 4 bytes at 100 % fill instead of cap slots of 8 more bytes
@@ -1445,8 +1431,7 @@ bool partitioned_preaggregate(Ctx *ctx, const PartAggSpec &spec, const PartAggIn
     // 3.35 -> 3.07 ms, the bucket pass itself 1.63 -> 1.60 ms with one workgroup per CU instead of three; C4: 489 ->
     // 245 buckets, scatter 2.12 -> 1.52 ms).  8192 slots (first row kept inside the COUNT cell, 16-byte slots) were
     // measured too: level 1 -0.1 ms, bucket pass +0.13 ms, nothing gained.
-    const char *dk_e = hook("SQLRS_LDS_DENSE_KB"); // tuning hook, read per call
-    const size_t dense_budget = (size_t)(dk_e ? std::atoi(dk_e) : 150) * 1024;
+    constexpr size_t dense_budget = 150 * 1024;
     const size_t dslot = 8 * (size_t)spec.n_acc + 4;
     uint32_t rbits = 8;
     while (rbits < 14 && ((size_t)2 << rbits) * dslot <= dense_budget) rbits++;
@@ -1586,9 +1571,9 @@ bool partitioned_preaggregate(Ctx *ctx, const PartAggSpec &spec, const PartAggIn
     int64_t nonempty_d = 0;
     for (uint32_t bkt = 0; bkt < P; bkt++) nonempty_d += pr.bucket_end(bkt) > hb[bkt];
     const int64_t avg = n / std::max<int64_t>(nonempty_d, 1);
-    const char *cd_e = hook("SQLRS_DENSE_CHUNK_DIV"), *sa_e = hook("SQLRS_DENSE_SPLIT_PCT"); // tuning hooks, read per call
+    const char *cd_e = hook("SQLRS_DENSE_CHUNK_DIV"); // tuning hook, read per call
     const int cdiv = cd_e ? std::max(1, std::atoi(cd_e)) : 2;        // chunk = average / this
-    const int sa_pct = sa_e ? std::max(1, std::atoi(sa_e)) : 125;    // buckets above this % of the average are split
+    constexpr int sa_pct = 125;                                      // buckets above this % of the average are split
     chunk = (uint32_t)std::max<int64_t>(32768, avg / cdiv);
     split_above = (uint32_t)std::max<int64_t>(65536, avg * sa_pct / 100);
   }

@@ -544,10 +544,7 @@ static bool agg_consume(sqlrs_hash_agg *a, int64_t n, const std::vector<DCol> &k
     }
     // ---- partition route ----------------------------------------------------------
     bool done = false;
-    static const int64_t PART_MIN_ROWS = [] {
-      const char *e = hook("SQLRS_PART_MIN_ROWS"); // test hook: force the partition route
-      return e ? std::atoll(e) : (1ll << 21);
-    }();
+    const int64_t PART_MIN_ROWS = 1ll << 21;
     if ((n >= PART_MIN_ROWS || js) && pcols.size() <= 2) {
       PartAggSpec spec;
       bool ok = true;

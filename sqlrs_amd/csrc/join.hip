@@ -315,13 +315,13 @@ static void build_table(sqlrs_hash_join *j) {
   const char *db1_e = hook("SQLRS_DENSE_BUILD_ONE_FETCH"); // A/B hook, read per call (0 = the two-fetch sequence below)
   // (the one-fetch form allocates the table of the LARGEST admissible range before it has looked at a key: only while that
   //  stays under 1 GiB — advisor r05; beyond, the two-fetch sequence below sizes the table from the range it has seen)
-  const uint64_t spk1 = j->lazy_table ? dense_slots_per_key_owned() : 4;
+  const uint64_t spk1 = j->lazy_table ? DENSE_SLOTS_PER_KEY_OWNED : 4;
   if (j->exact && n > 0 && n <= (1ll << 24) && 4 * (spk1 * (uint64_t)n + 1024) <= (1ull << 30) && j->key_dtype != SQLRS_FLOAT64 &&
       !(db1_e && std::atoi(db1_e) == 0)) {
     // one fetch (see dense_pack_count_kernel): the table is sized for the largest range that takes the route
     ProfScope ps(ctx, "join_build_dense");
     const char *pj_e = hook("SQLRS_DENSE_JOIN_SLOTS_PLAIN"); // tuning hook, read per call
-    const uint64_t slots_per_key = j->lazy_table ? dense_slots_per_key_owned() : (pj_e ? (uint64_t)std::max(1, std::atoi(pj_e)) : 4);
+    const uint64_t slots_per_key = j->lazy_table ? DENSE_SLOTS_PER_KEY_OWNED : (pj_e ? (uint64_t)std::max(1, std::atoi(pj_e)) : 4);
     const uint64_t max_range = slots_per_key * (uint64_t)n + 1024;
     uint32_t bits = 1;
     while (((1ull << bits) - 1) < (uint64_t)n) bits++; // all ones = empty must not be a build row
@@ -387,7 +387,7 @@ static void build_table(sqlrs_hash_join *j) {
       //  by key range and needs only the existence bitmap of the range — a filtered dimension, or the hash-partitioned
       //  shard of one that a rank of the multi-GPU plan receives, 1/8 of the keys of the range for 8 ranks)
       const char *pj_e = hook("SQLRS_DENSE_JOIN_SLOTS_PLAIN"); // tuning hook, read per call
-      const uint64_t slots_per_key = j->lazy_table ? dense_slots_per_key_owned() : (pj_e ? (uint64_t)std::max(1, std::atoi(pj_e)) : 4);
+      const uint64_t slots_per_key = j->lazy_table ? DENSE_SLOTS_PER_KEY_OWNED : (pj_e ? (uint64_t)std::max(1, std::atoi(pj_e)) : 4);
       if (range <= slots_per_key * (uint64_t)n + 1024 && range < (1ull << 31)) {
         ProfScope ps(ctx, "join_build_dense");
         BufP dense = ctx->alloc(4 * (size_t)range + 8);
@@ -560,8 +560,7 @@ __global__ __launch_bounds__(256) void dd_count_stream_kernel(const uint64_t *__
 }
 static bool build_dense_dup(sqlrs_hash_join *j) {
   Ctx *ctx = j->ctx;
-  const char *dd_e = hook("SQLRS_JOIN_DENSE_DUP"); // test / A-B hook, read per call: 0 = the general table
-  if ((dd_e && std::atoi(dd_e) == 0) || !j->dup_range || !j->exact || !j->bkeys || j->bkeys_validity || j->nB <= 0 ||
+  if (!j->dup_range || !j->exact || !j->bkeys || j->bkeys_validity || j->nB <= 0 ||
       j->nB > 0x7fffffffll || j->dup_range >= (1ull << 31))
     return false;
   const uint32_t *mult = hash_join_dup_mult(j);
@@ -734,7 +733,6 @@ static Pairs probe_pairs(sqlrs_hash_join *j, const NKeys &pk) {
         const int64_t every = std::max<int64_t>(1, n >> 14); // ~16 K sampled rows
         join_probe_dense_sample_kernel<<<dim3((unsigned)ceil_div(ceil_div(n, every), 256)), dim3(256), 0, ctx->stream>>>(
             pk.keys->as<uint64_t>(), n, every, dt, miss);
-        const char *sc_e = hook("SQLRS_PROBE_ALLHIT_SC1"); // A/B hook, read per call
         if (dt.packed) { // wave-contiguous chunks over the bit-packed table
           const unsigned pblocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n / JAP_ROWS, 4), JAP_GRID * (int64_t)ctx->num_cus));
           if (((uintptr_t)pk.keys->p & 15) == 0)
@@ -743,22 +741,16 @@ static Pairs probe_pairs(sqlrs_hash_join *j, const NKeys &pk) {
           else
             join_probe_dense_allhit_packed_kernel<false><<<dim3(pblocks), dim3(256), 0, ctx->stream>>>(pk.keys->as<uint64_t>(), n, dt, p.left->as<uint64_t>(),
                                                                                                     p.right->as<uint32_t>(), miss);
-        } else if (sc_e && std::atoi(sc_e) == 1)
-          join_probe_dense_allhit_kernel<true><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(pk.keys->as<uint64_t>(), n, dt, p.left->as<uint64_t>(),
-                                                                                          p.right->as<uint32_t>(), miss);
-        else
-          join_probe_dense_allhit_kernel<false><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(pk.keys->as<uint64_t>(), n, dt, p.left->as<uint64_t>(),
+        } else
+          join_probe_dense_allhit_kernel<<<dim3(blocks), dim3(256), 0, ctx->stream>>>(pk.keys->as<uint64_t>(), n, dt, p.left->as<uint64_t>(),
                                                                                            p.right->as<uint32_t>(), miss);
         SQ_HIP(hipGetLastError());
-        const char *hc_e = hook("SQLRS_PROBE_ALLHIT_HOSTCHECK"); // A/B hook, read per call (default on)
-        if (!(hc_e && std::atoi(hc_e) == 0)) {
-          if (ctx->fetch_value(miss) == 0) { // every pair is in place
-            p.m = n;
-            p.right_identity = true;
-            return p;
-          }
-          j->probe_miss_seen = true; // (later batches of this join go straight to the compacting kernel)
+        if (ctx->fetch_value(miss) == 0) { // every pair is in place
+          p.m = n;
+          p.right_identity = true;
+          return p;
         }
+        j->probe_miss_seen = true; // (later batches of this join go straight to the compacting kernel)
       }
     }
     BufP desc = ctx->alloc_zero(8 * (size_t)tiles + 24);
@@ -832,8 +824,7 @@ static Pairs probe_pairs(sqlrs_hash_join *j, const NKeys &pk) {
     lds_join_unpermute(j, lmg, n, outer_right, match->as<uint2>(), counts->as<uint32_t>(), grouped);
   } else if (j->dd_table) { // duplicate keys over a dense range: {run, rows} by direct address
     ProfScope ps(ctx, "join_probe_count_dense_dup");
-    const char *ds_e = hook("SQLRS_DD_STREAM"); // A/B hook, read per call: 0 = the one-row-per-lane form for every batch
-    if (!pk.validity && n >= JAP_ROWS && ((uintptr_t)pk.keys->p & 15) == 0 && !(ds_e && std::atoi(ds_e) == 0)) {
+    if (!pk.validity && n >= JAP_ROWS && ((uintptr_t)pk.keys->p & 15) == 0) {
       const unsigned pblocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n / JAP_ROWS, 4), JAP_GRID * (int64_t)ctx->num_cus));
       dd_count_stream_kernel<<<dim3(pblocks), dim3(256), 0, ctx->stream>>>(pk.keys->as<uint64_t>(), n, j->dup_min, j->dup_range, j->dd_table->as<uint32_t>(),
                                                                          outer_right, counts->as<uint32_t>(), match->as<uint2>(), grouped);
@@ -1000,8 +991,6 @@ const uint64_t *hash_join_dense_bits(sqlrs_hash_join *j) {
 // Key-only build side (see dense_bits_kernel): true = `out` holds the joined batch
 static bool semi_join_probe(sqlrs_hash_join *j, InBatch &ib, const NKeys &pk, DBatch *out) {
   Ctx *ctx = j->ctx;
-  const char *env_e = hook("SQLRS_SEMI_JOIN"); // test hook, read per call: 0 = never
-  if (env_e && std::atoi(env_e) == 0) return false;
   if (j->dense_pending && j->join_type == SQLRS_JOIN_INNER && !j->has_filter && j->left.cols.size() == 1) dense_resolve(j); // (a candidate: decide now)
   if (j->join_type != SQLRS_JOIN_INNER || j->has_filter || !j->unique || !j->dense || !j->exact || pk.validity ||
       j->left.cols.size() != 1 || j->lkeys.size() != 1 || j->lkeys[0].nodes.size() != 1 || j->rkeys[0].nodes.size() != 1 ||

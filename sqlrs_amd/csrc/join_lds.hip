@@ -455,9 +455,8 @@ static uint32_t lds_partition_keys(Ctx *ctx, const uint64_t *keys, int64_t n, Pa
   // load <= 1/2 in the fullest bucket.  (Round 6 tried <= 0.7, which puts C3's 1e6 build keys — 1953 per bucket, the fullest
   // ~2090 — on 4096-slot tables, two workgroups per CU instead of one: probe pass 0.54 -> 0.81 ms.  A wave's lookup takes as
   // long as the longest probe sequence among its 64 lanes, and that length, not the number of resident waves, sets the pace:
-  // without any lookup the pass takes 0.38 ms.  SQLRS_LJ_LOAD = percent, read once per join.)
-  const char *ld_e = hook("SQLRS_LJ_LOAD");
-  const uint32_t pct = ld_e ? (uint32_t)std::min(90, std::max(10, std::atoi(ld_e))) : 50;
+  // without any lookup the pass takes 0.38 ms.)
+  const uint32_t pct = 50;
   uint32_t slots = 1024;
   while ((uint64_t)slots * pct < 100ull * maxb) slots <<= 1;
   return slots <= 8192 ? slots : 0; // (8192 x 16 B = 128 KiB: one workgroup per CU)

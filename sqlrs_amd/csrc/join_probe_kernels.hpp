@@ -361,7 +361,6 @@ __global__ void join_probe_dense_sample_kernel(const uint64_t *__restrict__ keys
 }
 // thread t of the grid takes rows t, t + S, t + 2 S, ... (S = threads of the grid), JA_ILP of them per trip: the shape of
 // the composite micro-benchmark (per-wave contiguous chunks with clamped tails measured 9 % slower, 0.755 vs 0.69 ms)
-template <bool SC1>
 __global__ __launch_bounds__(256) void join_probe_dense_allhit_kernel(const uint64_t *__restrict__ keys, int64_t n, DenseTable dt,
                                                                       uint64_t *__restrict__ left_idx,
                                                                       uint32_t *__restrict__ right_idx,
@@ -376,10 +375,10 @@ __global__ __launch_bounds__(256) void join_probe_dense_allhit_kernel(const uint
     for (int u = 0; u < JA_ILP; u++) k[u] = __builtin_nontemporal_load(keys + i + u * S);
     uint32_t h[JA_ILP];
 #pragma unroll
-    for (int u = 0; u < JA_ILP; u++) { // (unconditional: out-of-range keys read heads[range + 1], always empty; SC1: agent-scope loads bypass the L1)
+    for (int u = 0; u < JA_ILP; u++) { // (unconditional: out-of-range keys read heads[range + 1], always empty)
       const uint64_t d = k[u] - dt.kmin;
       const uint32_t *hp = dt.heads + (d < dt.range ? d : dt.range + 1); // (never heads[range]: the NULL build row's slot)
-      h[u] = SC1 ? __hip_atomic_load(hp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *hp;
+      h[u] = *hp;
     }
 #pragma unroll
     for (int u = 0; u < JA_ILP; u++) {
@@ -610,10 +609,7 @@ __global__ __launch_bounds__(BLOCK) void join_probe_unique_outer_kernel(
   if (lane_id() == 0 && r < n) left_validity[r >> 6] = mm;
 }
 
-static uint64_t dense_slots_per_key_owned() {
-  const char *e = hook("SQLRS_DENSE_JOIN_SLOTS"); // test / tuning hook, read per call
-  return e ? (uint64_t)std::max(1, std::atoi(e)) : 16;
-}
+constexpr uint64_t DENSE_SLOTS_PER_KEY_OWNED = 16; // direct-address slots per build key for a join+aggregate's join (lazy_table)
 // min / max of the valid build keys as signed integers (dense-range detection)
 __global__ __launch_bounds__(256) void key_minmax_kernel(const uint64_t *__restrict__ keys, const uint64_t *__restrict__ validity,
                                   int64_t n, unsigned long long *mn, unsigned long long *mx) {

@@ -73,15 +73,13 @@ static bool order_wide(Ctx *ctx, const DCol &key, int desc, const DCol *carry, i
   BufP hist = ctx->alloc(4 * (size_t)(256 * nblocks)), offs = ctx->alloc(4 * (size_t)(256 * nblocks)), total = ctx->alloc(8);
   const uint64_t *psrc = (carry && !pay_rows) ? carry->v<uint64_t>() : nullptr;
   dim3 g1((unsigned)nblocks), g2((unsigned)ntmax), b(OW_WG);
-  const char *two_e = hook("SQLRS_ORDER_TWO"); // (read per call: 0 = word and payload side by side in LDS, two workgroups per CU)
-  const bool two = !(two_e && two_e[0] == '0');
   // The first pass in its look-back form (the narrow route's, see ow_scatter_kernel): its 256 segment sizes from one persistent
   // launch, the tiles chained — no count matrix, no scan.  The second pass keeps its counting form: its digit is a search in the
   // row's own segment's splitters, so nothing ahead of the first pass can count it.  SQLRS_ORDER_LB=0 (read per call) / a spin
   // that ran out: the counting form.
   static thread_local bool wide_lb_skip = false;
   const char *lb_e = hook("SQLRS_ORDER_LB"), *lbf_e = hook("SQLRS_ORDER_LB_TEST_FAIL");
-  const bool lb1 = rec1 && two && n < (1ll << 30) && !g_order_lb_off.load() && !wide_lb_skip && !(lb_e && lb_e[0] == '0');
+  const bool lb1 = rec1 && n < (1ll << 30) && !g_order_lb_off.load() && !wide_lb_skip && !(lb_e && lb_e[0] == '0');
   BufP ghb1, lbdesc1;
   if (lb1) {
     ProfScope ps(ctx, "order_split");
@@ -101,12 +99,9 @@ static bool order_wide(Ctx *ctx, const DCol &key, int desc, const DCol *carry, i
     owk_hist_kernel<KIND, 1><<<g1, b, 0, ctx->stream>>>(key.values, n, desc, imin, nblocks, hist->as<uint32_t>(), nullptr, subp, nk1, tfp);
     SQ_HIP(hipGetLastError());
     exclusive_scan_u32(ctx, hist->as<uint32_t>(), 256 * nblocks, nullptr, offs->as<uint32_t>(), total->as<uint64_t>());
-    if (rec1 && two)
+    if (rec1)
       owk_scatter_kernel<KIND, 1, 1, true, false, true><<<g1, b, 0, ctx->stream>>>(key.values, psrc, n, desc, imin, nblocks, offs->as<uint32_t>(),
                                                                                   w1->as<uint64_t>(), nullptr, nullptr, subp, nk1, tfp);
-    else if (rec1)
-      owk_scatter_kernel<KIND, 1, 1, true><<<g1, b, 0, ctx->stream>>>(key.values, psrc, n, desc, imin, nblocks, offs->as<uint32_t>(),
-                                                                     w1->as<uint64_t>(), nullptr, nullptr, subp, nk1, tfp);
     else if (has_pay)
       owk_scatter_kernel<KIND, 1, 1, false><<<g1, b, 0, ctx->stream>>>(key.values, psrc, n, desc, imin, nblocks, offs->as<uint32_t>(),
                                                                       w1->as<uint64_t>(), p1->as<uint64_t>(), nullptr, subp, nk1, tfp);
@@ -130,18 +125,12 @@ static bool order_wide(Ctx *ctx, const DCol &key, int desc, const DCol *carry, i
     else owk_hist_kernel<KIND, 2><<<g2, b, 0, ctx->stream>>>(w1->p, n, desc, imin, ntmax, hist2->as<uint32_t>(), tp, subp, nk1, tfp);
     SQ_HIP(hipGetLastError());
     exclusive_scan_u32(ctx, hist2->as<uint32_t>(), 256 * ntmax, nullptr, offs2->as<uint32_t>(), total->as<uint64_t>());
-    if (rec1 && two)
+    if (rec1)
       owk_scatter_kernel<KIND, 2, 1, true, true, true><<<g2, b, 0, ctx->stream>>>(w1->p, nullptr, n, desc, imin, ntmax, offs2->as<uint32_t>(),
                                                                                  out2->as<uint64_t>(), nullptr, tp, subp, nk1, tfp);
-    else if (rec1)
-      owk_scatter_kernel<KIND, 2, 1, true, true><<<g2, b, 0, ctx->stream>>>(w1->p, nullptr, n, desc, imin, ntmax, offs2->as<uint32_t>(),
-                                                                           out2->as<uint64_t>(), nullptr, tp, subp, nk1, tfp);
-    else if (has_pay && two)
+    else if (has_pay)
       owk_scatter_kernel<KIND, 2, 1, true, false, true><<<g2, b, 0, ctx->stream>>>(w1->p, p1->as<uint64_t>(), n, desc, imin, ntmax, offs2->as<uint32_t>(),
                                                                                   out2->as<uint64_t>(), nullptr, tp, subp, nk1, tfp);
-    else if (has_pay)
-      owk_scatter_kernel<KIND, 2, 1, true><<<g2, b, 0, ctx->stream>>>(w1->p, p1->as<uint64_t>(), n, desc, imin, ntmax, offs2->as<uint32_t>(),
-                                                                     out2->as<uint64_t>(), nullptr, tp, subp, nk1, tfp);
     else
       owk_scatter_kernel<KIND, 2, 0, false><<<g2, b, 0, ctx->stream>>>(w1->p, nullptr, n, desc, imin, ntmax, offs2->as<uint32_t>(),
                                                                       out2->as<uint64_t>(), nullptr, tp, subp, nk1, tfp);
@@ -171,9 +160,6 @@ static bool order_wide(Ctx *ctx, const DCol &key, int desc, const DCol *carry, i
     } skip;
     return order_wide<KIND>(ctx, key, desc, carry, n, imin, range, key_out, carry_out, perm_out, want_perm);
   }
-  if (hook("SQLRS_ORDER_TRACE"))
-    std::fprintf(stderr, "[order_wide] n=%lld key bits=%d groups=%u largest group to sort=%u rows, %u chunks of single-value groups\n",
-                 (long long)n, kb, G, max_group, pure_chunks);
   if (max_group > FIN_CAP) return false; // thousands of distinct keys between two neighbouring samples: general path
   // 4. finish
   key_out->dtype = key.dtype;
@@ -283,13 +269,8 @@ static bool order_fast_impl(Ctx *ctx, const DCol &key, int desc, const DCol *car
     else {
       // (sampled extremes are not the extremes, and this route does not need them: offsets from 0 over the whole 64-bit
       //  range do — the first and the last group then span far more values than their rows use, which their workgroups
-      //  notice as one long run of equal top bits and sort on all bits.  SQLRS_ORDER_WIDE_EXACT=1: the exact pass first)
+      //  notice as one long run of equal top bits and sort on all bits)
       if (optimistic) {
-        const char *ex = hook("SQLRS_ORDER_WIDE_EXACT");
-        if (ex && ex[0] == '1') {
-          *retry_exact = true;
-          return false;
-        }
         imin = 0;
         range = ~0ull;
       }
@@ -451,19 +432,15 @@ static bool order_fast_impl(Ctx *ctx, const DCol &key, int desc, const DCol *car
     const unsigned gblocks = (unsigned)std::min<int64_t>(nblocks, 4 * (int64_t)ctx->num_cus);
     ow_ghist_kernel<KIND><<<dim3(gblocks), b, 0, ctx->stream>>>(src, n, desc, imin, s1, s2, nblocks, gh, oob_lb, kbits);
     uint64_t *out1 = NPAY == 1 ? recbuf1->as<uint64_t>() : wdst, *out2 = NPAY == 1 ? recbuf->as<uint64_t>() : walt; // (records / words)
-    const char *two_e = hook("SQLRS_ORDER_TWO"); // (read per call: 0 = word and value side by side in LDS, two workgroups per CU)
-    const bool two = NPAY == 1 && !(two_e && two_e[0] == '0');
+    // (a carried column: word and value take turns in one LDS tile, the TWO form of ow_scatter_kernel)
     const char *slim_e = hook("SQLRS_ORDER_SLIM"); // (A/B hook, read per call: 0 = 16-byte records {word, value} between the passes)
-    slim = two && !want_perm && !(slim_e && slim_e[0] == '0'); // 12-byte records {key offset, value}: nobody reads the row id
+    slim = NPAY == 1 && !want_perm && !(slim_e && slim_e[0] == '0'); // 12-byte records {key offset, value}: nobody reads the row id
     if (slim)
       ow_scatter_kernel<KIND, true, NPAY, false, NPAY == 1, false, true, NPAY == 1, NPAY == 1><<<g, b, 0, ctx->stream>>>(
           src, psrc, n, desc, imin, s1, nblocks, nullptr, out1, nullptr, nullptr, oob_lb, gh, lbdesc->as<uint32_t>(), nullptr, lbw);
-    else if (two)
+    else
       ow_scatter_kernel<KIND, true, NPAY, false, NPAY == 1, false, true, NPAY == 1><<<g, b, 0, ctx->stream>>>(
           src, psrc, n, desc, imin, s1, nblocks, nullptr, out1, nullptr, nullptr, oob_lb, gh, lbdesc->as<uint32_t>(), nullptr, lbw);
-    else
-    ow_scatter_kernel<KIND, true, NPAY, false, NPAY == 1, false, true><<<g, b, 0, ctx->stream>>>(
-        src, psrc, n, desc, imin, s1, nblocks, nullptr, out1, nullptr, nullptr, oob_lb, gh, lbdesc->as<uint32_t>(), nullptr, lbw);
     if (lbf_e && lbf_e[0] == '2') { // test hook: as if a spin had run out in the first pass — its output is garbage, the flag is up
       SQ_HIP(hipMemsetAsync(out1, 0xff, (NPAY == 1 ? 16 : 8) * (size_t)n, ctx->stream));
       SQ_HIP(hipMemsetAsync(lbw, 1, 4, ctx->stream));
@@ -478,14 +455,10 @@ static bool order_fast_impl(Ctx *ctx, const DCol &key, int desc, const DCol *car
       ow_scatter_kernel<KIND, false, NPAY, true, NPAY == 1, NPAY == 1, true, NPAY == 1, NPAY == 1><<<dim3((unsigned)ntmax), b, 0, ctx->stream>>>(
           out1, nullptr, n, desc, imin, s2, ntmax, nullptr, out2, nullptr, (const OwTile *)tiles2->p, oob_lb, gh + 256,
           lbdesc->as<uint32_t>() + 256 * (size_t)nblocks, boundb->as<uint32_t>(), lbw);
-    else if (two)
+    else
       ow_scatter_kernel<KIND, false, NPAY, true, NPAY == 1, NPAY == 1, true, NPAY == 1><<<dim3((unsigned)ntmax), b, 0, ctx->stream>>>(
           out1, nullptr, n, desc, imin, s2, ntmax, nullptr, out2, nullptr, (const OwTile *)tiles2->p, oob_lb, gh + 256,
           lbdesc->as<uint32_t>() + 256 * (size_t)nblocks, boundb->as<uint32_t>(), lbw);
-    else
-    ow_scatter_kernel<KIND, false, NPAY, true, NPAY == 1, NPAY == 1, true><<<dim3((unsigned)ntmax), b, 0, ctx->stream>>>(
-        out1, nullptr, n, desc, imin, s2, ntmax, nullptr, out2, nullptr, (const OwTile *)tiles2->p, oob_lb, gh + 256,
-        lbdesc->as<uint32_t>() + 256 * (size_t)nblocks, boundb->as<uint32_t>(), lbw);
     SQ_HIP(hipGetLastError());
     src = out2;
     psrc = nullptr;

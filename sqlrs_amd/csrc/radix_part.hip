@@ -101,11 +101,8 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
   if (P_wanted > 512) { // one level handles up to 512 digits (runs of >= 8 rows per tile)
     // split the digits evenly between the two levels: 2^p2_bits second-level digits with
     // 2^p2_bits >= sqrt(P) (runs get longer as a level's digit count drops)
-    const char *p2_e = hook("SQLRS_RP_P2BITS"); // tuning hook, read per call (in-process A/B)
-    const int p2_env = p2_e ? std::atoi(p2_e) : 0;
     p2_bits = 5;
     while (p2_bits < 8 && (1u << (2 * p2_bits)) < P_wanted) p2_bits++;
-    if (p2_env >= 4 && p2_env <= 9) p2_bits = (uint32_t)p2_env;
     d1 = (uint32_t)ceil_div(P_wanted, 1u << p2_bits);
     if (d1 > 512) {
       p2_bits = 8;
@@ -116,7 +113,7 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
     // level 2.  Level 2 gains more from its longer runs than level 1 loses (C5 with sparse keys, same process:
     // 7.93 + 6.67 -> 7.80 + 6.26 ms); the bucket layout of the result does not depend on the split.  The arena
     // slack of 512 digits must still be a fraction of the input (see `chunked` below).
-    if (!p2_e && p2_bits == 8 && 2 * d1 <= 512 && !in.key_validity && !in.val_validity[0] && !in.val_validity[1] &&
+    if (p2_bits == 8 && 2 * d1 <= 512 && !in.key_validity && !in.val_validity[0] && !in.val_validity[1] &&
         2ull * std::min<uint64_t>((uint64_t)ceil_div(n, 6144), (uint64_t)ctx->num_cus) * (2 * d1) * 6144ull <= 2 * (uint64_t)n) {
       p2_bits = 7;
       d1 = (uint32_t)ceil_div(P_wanted, 1u << p2_bits);
@@ -132,20 +129,14 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
   out->pack = kp;
   out->rec = nullptr;
   const int WG = 512;
-  // rows per thread: 12 -> 6144-row tiles, 8 -> 4096-row tiles (two value columns); one
+  // rows per thread: 8 -> 4096-row tiles for two value columns, 12 -> 6144-row tiles otherwise; one
   // workgroup per CU either way (the staging area is ~140 KiB)
-  const char *rows_e = hook("SQLRS_RP_ROWS"); // tuning only, read per call (in-process A/B)
-  const int rows_env = rows_e ? std::atoi(rows_e) : 0;
-  // 16 = 8192-row tiles (packed rows with one value column only: 128 KiB of staging, 256 VGPRs, no spills): the
-  // default for very large batches — a third fewer barrier rounds per row (C5, one process: level 1 5.50 -> 5.36 ms,
-  // level 2 3.66 -> 3.61 ms); smaller batches keep 6144-row tiles (less arena slack, more tiles per workgroup)
-  // (two-level partitions only — the counting single level is slower with them, C4: 1.55 -> 1.96 ms — and not with the
-  //  predicate on a column of its own: that instantiation needs more than 256 VGPRs and spills)
-  // Round 5: the slim first level runs 768-thread workgroups over 6144-row tiles by default (twelve waves per CU instead of
-  // eight, 159 VGPRs, no spill: C5 level 1 5.33 (8192-row tiles, 512 threads) / 5.39 (6144, 512) -> 4.95 ms in one process,
-  // step 10.45 -> 10.10; 1024 threads x 6 rows: the same 4.98 with 3 spilled registers).  8192-row tiles only on request.
-  const bool big16 = pack && nv == 1 && rows_env == 16;
-  const int ROWS = nv > 1 ? 8 : (rows_env == 6 ? 6 : ((rows_env == 8 && pack) ? 8 : (big16 ? 16 : 12)));
+  // (measured against 8192-row tiles, 16 rows per thread, for packed rows with one value column — 128 KiB of staging, 256 VGPRs,
+  //  no spills, a third fewer barrier rounds per row: the slim first level with 768-thread workgroups over 6144-row tiles (twelve
+  //  waves per CU instead of eight, 159 VGPRs, no spill) takes 4.95 ms for C5 against 5.33 (8192-row tiles, 512 threads) / 5.39
+  //  (6144, 512) in one process, step 10.45 -> 10.10; 1024 threads x 6 rows: the same 4.98 with 3 spilled registers; the counting
+  //  single level is slower with 8192-row tiles, C4: 1.55 -> 1.96 ms)
+  const int ROWS = nv > 1 ? 8 : 12;
   const int RP_TILE = WG * ROWS;
   const size_t lds = (size_t)RP_TILE * (pack ? 8 * (1 + nv) : 8 * (1 + nv) + 4 + 2 + 1) + (size_t)WG * (4 + 4 + 8);
 
@@ -157,7 +148,7 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
   // of ~24 rows covers three cache lines instead of 2 x 1.5 (C5: level 2 4.93 -> 4.26 ms, bucket pass 1.81 ->
   // 1.67 ms in one process)
   const char *rec_e = hook("SQLRS_RP_REC"); // read per call: 0 = column form (in-process A/B, tools/ab_in_process.py)
-  const bool use_rec = pack && nv == 1 && (ROWS == 12 || ROWS == 16) && !(rec_e && std::atoi(rec_e) == 0);
+  const bool use_rec = pack && nv == 1 && !(rec_e && std::atoi(rec_e) == 0);
   struct Cols {
     BufP k, v0, v1, idx, fl, rec;
   };
@@ -206,7 +197,7 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
       ProfScope ps(ctx, in.build_side ? "rp_hist_build" : "rp_hist");
 #define SQ_RH1(R, PL) rp_hist_kernel<512, R, PL><<<dim3(nt), dim3(512), 0, ctx->stream>>>(rin.key, rin.key_validity, rin.flags, tp, P, p2_bits, level, digits, mat->as<uint32_t>(), kp)
 #define SQ_RH(R) do { if (!rin.key_validity && !rin.flags) SQ_RH1(R, true); else SQ_RH1(R, false); } while (0)
-      if (ROWS == 12) SQ_RH(12); else if (ROWS == 16) SQ_RH(16); else if (ROWS == 8) SQ_RH(8); else SQ_RH(6);
+      if (ROWS == 12) SQ_RH(12); else SQ_RH(8);
 #undef SQ_RH
 #undef SQ_RH1
       SQ_HIP(hipGetLastError());
@@ -229,31 +220,18 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
     if (nt) {
       ProfScope ps(ctx, in.build_side ? "rp_scatter_build" : "rp_scatter");
       // one workgroup per CU slot; contiguous tile ranges (8 per workgroup at least)
-      uint32_t wgs = std::min<uint32_t>(nt, (uint32_t)ctx->num_cus * ((ROWS == 6 || (ROWS == 8 && pack)) ? 2 : 1));
+      uint32_t wgs = std::min<uint32_t>(nt, (uint32_t)ctx->num_cus);
       uint32_t tpw = (uint32_t)ceil_div(nt, wgs);
       wgs = (uint32_t)ceil_div(nt, tpw);
       dim3 g(wgs), b((unsigned)WG);
       const int mode = level == 1 ? (flags ? RP_L1_NULL : RP_L1) : (flags ? RP_LN_FLAG : RP_LN);
       if (slim) {
         const size_t slds = (size_t)RP_TILE * 13 + 1024 + (size_t)WG * 16 + 512 + 128;
-        // (1024-thread workgroups over the same 8192-row tile, eight rows per thread — sixteen waves per CU as in the bucket pass —
+        // (1024-thread workgroups over an 8192-row tile, eight rows per thread — sixteen waves per CU as in the bucket pass —
         //  were measured in round 5: 128 VGPRs, 17 spilled, level 2 3.00 -> 3.21 ms in one process; not kept)
-        if (ROWS == 16) {
-          auto kfn = rp_scatter_slim_kernel<512, 16>;
-          allow_big_lds(ctx, kfn);
-          kfn<<<g, b, slds, ctx->stream>>>(slim->in, slim->out, tp, p2_bits, digits, offs_tm->as<uint32_t>(), nt, tpw, sink,
-                                          slim->kshift, slim->rbits);
-        } else if (hook("SQLRS_RP_L2_WG") && std::atoi(hook("SQLRS_RP_L2_WG")) == 768) { // A/B hook, read per call
-          auto kfn = rp_scatter_slim_kernel<768, 8>;
-          allow_big_lds(ctx, kfn);
-          kfn<<<g, dim3(768), slds + 256 * 16, ctx->stream>>>(slim->in, slim->out, tp, p2_bits, digits, offs_tm->as<uint32_t>(), nt, tpw, sink,
-                                                            slim->kshift, slim->rbits);
-        } else {
-          auto kfn = rp_scatter_slim_kernel<512, 12>;
-          allow_big_lds(ctx, kfn);
-          kfn<<<g, b, slds, ctx->stream>>>(slim->in, slim->out, tp, p2_bits, digits, offs_tm->as<uint32_t>(), nt, tpw, sink,
-                                          slim->kshift, slim->rbits);
-        }
+        allow_big_lds(ctx, rp_scatter_slim_kernel);
+        rp_scatter_slim_kernel<<<g, b, slds, ctx->stream>>>(slim->in, slim->out, tp, p2_bits, digits, offs_tm->as<uint32_t>(), nt, tpw, sink,
+                                                           slim->kshift, slim->rbits);
         SQ_HIP(hipGetLastError());
         slim->total = total;
         *offs_out = offs;
@@ -261,7 +239,7 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
       }
 #define SQ_RP1(NV, R, M, PK)                                                                                  \
   do {                                                                                                        \
-    constexpr bool can_rec = NV == 1 && PK && (R == 12 || R == 16);                                           \
+    constexpr bool can_rec = NV == 1 && PK;                                                                   \
     auto kfn = rp_scatter_kernel<NV, 512, R, M, PK>;                                                          \
     if (can_rec && rout.rec) kfn = rp_scatter_kernel<NV, 512, R, M, PK, can_rec>;                             \
     allow_big_lds(ctx, kfn);                                                                                  \
@@ -276,11 +254,8 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
     else SQ_RP1(NV, R, RP_LN_FLAG, false);                                                                    \
   } while (0)
       if (nv == 2) SQ_RP(2, 8);
-      else if (ROWS == 6) { if (nv == 0) SQ_RP(0, 6); else SQ_RP(1, 6); }
-      else if (ROWS == 8) { if (nv == 0) SQ_RP(0, 8); else SQ_RP(1, 8); }
-      else if (ROWS == 16) { if (pack && mode == RP_LN) SQ_RP1(1, 16, RP_LN, true); else SQ_RP1(1, 16, RP_L1, true); }
       // (768 threads x 8 rows for the counting level 2 of hashed partitions: measured in round 5, 6.08 vs 6.08 ms — not kept)
-      else { if (nv == 0) SQ_RP(0, 12); else SQ_RP(1, 12); }
+      else if (nv == 0) SQ_RP(0, 12); else SQ_RP(1, 12);
 #undef SQ_RP1
 #undef SQ_RP
       SQ_HIP(hipGetLastError());
@@ -356,7 +331,7 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
   // row for a key of its own).
   const char *claim_e = hook("SQLRS_RP_CLAIM"); // test / tuning hook, read per call: 0 = never, 1 = whatever the batch size
   const int claim_env = claim_e ? std::atoi(claim_e) : -1;
-  const bool claimable = p2_bits == 0 && pack && kp.dense && nv <= 1 && ROWS == 12 && P <= (uint32_t)WG && P >= 2 &&
+  const bool claimable = p2_bits == 0 && pack && kp.dense && nv <= 1 && P <= (uint32_t)WG && P >= 2 &&
                          claim_env != 0 && (claim_env == 1 || n >= (1ll << 22));
   if (claimable) {
     const uint32_t tiles1c = (uint32_t)ceil_div(n, RP_TILE);
@@ -403,15 +378,10 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
       if (claim_slim) {
         uint32_t log_b = 0;
         while ((1u << log_b) < B) log_b++;
-#ifdef SLIM_AOS
-        csl.buf0 = ctx->alloc(sizeof(SlimRec) * (size_t)pool_rows);
-        csl.rows.rec = csl.buf0->as<SlimRec>();
-#else
         csl.buf0 = ctx->alloc(8 * (size_t)pool_rows);
         csl.buf1 = ctx->alloc(4 * (size_t)pool_rows);
         csl.rows.v = csl.buf0->as<uint64_t>();
         csl.rows.w = csl.buf1->as<uint32_t>();
-#endif
         csl.blk_bt = ctx->alloc(4 * (size_t)((slots_max >> log_b) + 2));
         csl.log_b = log_b;
         csl.tile = (uint32_t)RP_TILE;
@@ -461,26 +431,19 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
           const char *sd_e = hook("SQLRS_RP_SLIM_DELTA"); // test hook, read per call: blocks abandoned after fewer tiles
           so.max_delta = sd_e ? (uint32_t)std::max(1, std::min(std::atoi(sd_e), 127)) : 127u;
           const size_t slds = (size_t)RP_TILE * (8 + 4 + 2) + (size_t)WG * (4 + 4 + 8 + 8 + 4);
-          // 768-thread workgroups (twelve waves on the same 6144-row tile, 159 VGPRs, no spill) by default: C4 scatter 1.49 -> 1.43 ms,
-          // with the WHERE fused 1.31 -> 1.14 (one process, three rounds); SQLRS_RP_CLAIM_WG=512 (read per call) = the eight-wave form
-          const char *cwg_e = hook("SQLRS_RP_CLAIM_WG");
-          const bool wg768 = psrc != 3 && !(cwg_e && std::atoi(cwg_e) == 512); // (own predicate column: 4 spilled registers at 768)
+          // 768-thread workgroups (twelve waves on the same 6144-row tile, 159 VGPRs, no spill) instead of the eight-wave form: C4 scatter
+          // 1.49 -> 1.43 ms, with the WHERE fused 1.31 -> 1.14 (one process, three rounds); a predicate column of its own keeps the
+          // eight-wave form (4 spilled registers at 768)
           const size_t slds768 = (size_t)RP_TILE * (8 + 4 + 2) + (size_t)768 * (4 + 4 + 8 + 8 + 4);
-#define SQ_CS(PS)                                                                                                   \
+#define SQ_CS(W, R, PS, LDS)                                                                                        \
   do {                                                                                                              \
-    if (wg768) {                                                                                                    \
-      auto kfn = rp_claim_scatter_slim_kernel<768, 8, PS>;                                                          \
-      allow_big_lds(ctx, kfn);                                                                                      \
-      kfn<<<dim3(wgs), dim3(768), slds768, ctx->stream>>>(k, a0, in.filter, n, so, P, tiles1c, tpw, sink, kp);      \
-    } else {                                                                                                        \
-      auto kfn = rp_claim_scatter_slim_kernel<512, 12, PS>;                                                         \
-      allow_big_lds(ctx, kfn);                                                                                      \
-      kfn<<<dim3(wgs), dim3(512), slds, ctx->stream>>>(k, a0, in.filter, n, so, P, tiles1c, tpw, sink, kp);         \
-    }                                                                                                               \
+    auto kfn = rp_claim_scatter_slim_kernel<W, R, PS>;                                                              \
+    allow_big_lds(ctx, kfn);                                                                                        \
+    kfn<<<dim3(wgs), dim3(W), LDS, ctx->stream>>>(k, a0, in.filter, n, so, P, tiles1c, tpw, sink, kp);              \
   } while (0)
-          if (psrc < 0) SQ_CS(-1);
-          else if (psrc == 1) SQ_CS(1);
-          else SQ_CS(3);
+          if (psrc < 0) SQ_CS(768, 8, -1, slds768);
+          else if (psrc == 1) SQ_CS(768, 8, 1, slds768);
+          else SQ_CS(512, 12, 3, slds);
 #undef SQ_CS
         } else if (nv == 0) SQ_CL(0, false);
         else if (use_rec) SQ_CL(1, true);
@@ -525,11 +488,7 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
   const uint32_t ctpw = (uint32_t)ceil_div(tiles1, std::max(cwgs, 1u));
   cwgs = (uint32_t)ceil_div(tiles1, std::max(ctpw, 1u));
   const uint64_t spare_chunks = (uint64_t)cwgs * (d1 + 1); // chunks that may stay partly filled or unused
-  static const int ct_env = [] { // tuning hook: tiles per chunk (1, 4, 8, 16 measured alike: 1 = smallest reservation)
-    const char *e = hook("SQLRS_RP_CHUNK_TILES");
-    return e ? std::max(1, std::min(64, std::atoi(e))) : 1;
-  }();
-  const uint64_t CAP = (uint64_t)RP_TILE * (uint64_t)ct_env;
+  const uint64_t CAP = (uint64_t)RP_TILE; // one tile per chunk (1, 4, 8, 16 measured alike: 1 = smallest reservation)
   bool chunked = p2_bits != 0 && !flags && chunk_env != 0 && d1 <= (uint32_t)WG &&
                  (chunk_env == 1 || spare_chunks * CAP <= (uint64_t)n); // (the slack of the arenas is a fraction of the input)
   if (in.filter.col && !chunked) return false; // only the chunked first level evaluates a row filter
@@ -538,14 +497,14 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
     // "slim records" above): dense packed rows with one value column whose chunk histograms fit LDS, bucket tables of
     // <= 4096 slots.  SQLRS_RP_SLIM=0 (read per call) keeps the 16-byte form (in-process A/B, tests).
     const char *slim_e = hook("SQLRS_RP_SLIM");
-    const bool slim_on = pack && kp.dense && nv == 1 && (ROWS == 12 || ROWS == 16) && ct_env == 1 && (size_t)P * 4 <= 24 * 1024 &&
+    const bool slim_on = pack && kp.dense && nv == 1 && (size_t)P * 4 <= 24 * 1024 &&
                          kp.rbits + SLIM_LOCAL_BITS + 7 <= 32 && kp.rbits + p2_bits + SLIM_LOCAL_BITS <= 32 &&
                          !(slim_e && std::atoi(slim_e) == 0) && !(hook("SQLRS_RP_H2") && std::atoi(hook("SQLRS_RP_H2")) == 0);
     // arena mode: a workgroup fills at most ceil(its rows / CAP) chunks completely and leaves <= d1 partly filled
     // (slim: + the chunks closed early because their next run would be more than SLIM_RUNS - 1 tiles after their first)
     const char *sd_e = hook("SQLRS_RP_SLIM_DELTA"); // test hook, read per call: early closes at test sizes
     const uint32_t slim_delta = sd_e ? (uint32_t)std::max(1, std::min<int>(std::atoi(sd_e), (int)SLIM_RUNS - 1)) : SLIM_RUNS - 1;
-    const uint64_t arena = (uint64_t)ceil_div((int64_t)ctpw, (int64_t)ct_env) + d1 + 1 +
+    const uint64_t arena = (uint64_t)ctpw + d1 + 1 +
                            (slim_on ? (uint64_t)d1 * (uint64_t)ceil_div((int64_t)ctpw, (int64_t)slim_delta + 1) : 0);
     const uint64_t max_chunks = arena * cwgs;
     if (max_chunks * (CAP + RP_CHUNK_SKEW) + WG * (uint64_t)cwgs > 0xffffffffull) { // Tile::start is 64-bit, rows index u32 math
@@ -557,15 +516,10 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
       const uint32_t digits2 = 1u << p2_bits;
       auto slim_alloc = [&](size_t rows, BufP &b0, BufP &b1) {
         SlimRowsView v;
-#ifdef SLIM_AOS
-        b0 = ctx->alloc(sizeof(SlimRec) * rows);
-        v.rec = b0->as<SlimRec>();
-#else
         b0 = ctx->alloc(8 * rows);
         b1 = ctx->alloc(4 * rows);
         v.v = b0->as<uint64_t>();
         v.w = b1->as<uint32_t>();
-#endif
         return v;
       };
       BufP cb0, cb1;
@@ -597,41 +551,17 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
       {
         ProfScope ps(ctx, in.filter.col ? "rp_chunk_scatter_filter" : "rp_chunk_scatter");
         const int64_t sink = (int64_t)max_chunks * (CAP + RP_CHUNK_SKEW);
-#define SQ_SL1(R, PS)                                                                                                \
+        // (a predicate column of its own keeps the eight-wave form, 512 threads x 12 rows)
+        const size_t clds768 = (size_t)RP_TILE * 14 + (size_t)768 * (4 + 4 + 8 + 8 + 4 + 4) + (size_t)P * 4;
+#define SQ_SL(W, R, PS, LDS)                                                                                        \
   do {                                                                                                              \
-    auto kfn = rp_chunk_scatter_slim_kernel<512, R, PS>;                                                            \
+    auto kfn = rp_chunk_scatter_slim_kernel<W, R, PS>;                                                              \
     allow_big_lds(ctx, kfn);                                                                                        \
-    kfn<<<dim3(cwgs), dim3(512), clds, ctx->stream>>>(in.keys, (const uint64_t *)in.vals[0], in.filter, n, so, P, p2_bits, d1, \
-                                                      tiles1, ctpw, sink, kp);                                      \
+    kfn<<<dim3(cwgs), dim3(W), LDS, ctx->stream>>>(in.keys, (const uint64_t *)in.vals[0], in.filter, n, so, P, p2_bits, d1, \
+                                                   tiles1, ctpw, sink, kp);                                         \
   } while (0)
-#define SQ_SL(R) do { if (psrc < 0) SQ_SL1(R, -1); else if (psrc == 1) SQ_SL1(R, 1); else SQ_SL1(R, 3); } while (0)
-        const char *l1wg_e = hook("SQLRS_RP_L1_WG"); // A/B hook, read per call: 512 = the eight-wave form, 1024 x 6 rows
-        const int l1wg = l1wg_e ? std::atoi(l1wg_e) : 768;
-        if (ROWS == 12 && psrc != 3 && l1wg == 1024) {
-          const size_t clds1k = (size_t)RP_TILE * 14 + (size_t)1024 * (4 + 4 + 8 + 8 + 4 + 4) + (size_t)P * 4;
-          if (psrc < 0) {
-            auto kfn = rp_chunk_scatter_slim_kernel<1024, 6, -1>;
-            allow_big_lds(ctx, kfn);
-            kfn<<<dim3(cwgs), dim3(1024), clds1k, ctx->stream>>>(in.keys, (const uint64_t *)in.vals[0], in.filter, n, so, P, p2_bits, d1, tiles1, ctpw, sink, kp);
-          } else {
-            auto kfn = rp_chunk_scatter_slim_kernel<1024, 6, 1>;
-            allow_big_lds(ctx, kfn);
-            kfn<<<dim3(cwgs), dim3(1024), clds1k, ctx->stream>>>(in.keys, (const uint64_t *)in.vals[0], in.filter, n, so, P, p2_bits, d1, tiles1, ctpw, sink, kp);
-          }
-        } else if (ROWS == 12 && psrc != 3 && l1wg == 768) {
-          const size_t clds768 = (size_t)RP_TILE * 14 + (size_t)768 * (4 + 4 + 8 + 8 + 4 + 4) + (size_t)P * 4;
-          if (psrc < 0) {
-            auto kfn = rp_chunk_scatter_slim_kernel<768, 8, -1>;
-            allow_big_lds(ctx, kfn);
-            kfn<<<dim3(cwgs), dim3(768), clds768, ctx->stream>>>(in.keys, (const uint64_t *)in.vals[0], in.filter, n, so, P, p2_bits, d1, tiles1, ctpw, sink, kp);
-          } else {
-            auto kfn = rp_chunk_scatter_slim_kernel<768, 8, 1>;
-            allow_big_lds(ctx, kfn);
-            kfn<<<dim3(cwgs), dim3(768), clds768, ctx->stream>>>(in.keys, (const uint64_t *)in.vals[0], in.filter, n, so, P, p2_bits, d1, tiles1, ctpw, sink, kp);
-          }
-        } else if (ROWS == 16) SQ_SL(16); else SQ_SL(12);
+        if (psrc < 0) SQ_SL(768, 8, -1, clds768); else if (psrc == 1) SQ_SL(768, 8, 1, clds768); else SQ_SL(512, 12, 3, clds);
 #undef SQ_SL
-#undef SQ_SL1
         SQ_HIP(hipGetLastError());
       }
       // level-2 geometry from the chunk table, on the device (as below)
@@ -730,11 +660,10 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
       // chunk histograms of the next level counted by this kernel (H2): every bucket needs a 4-byte counter in LDS
       const char *h2_e = hook("SQLRS_RP_H2"); // A/B hook, read per call: 0 = level 2 runs its own histogram pass
       // (round 6: unpacked rows of hashed partitions too, on the 512-thread tile — its 22-byte staging rows leave 16 KiB: P <= ~3000
-      //  buckets, C4 over general keys; 65 536 buckets — the sparse-key C5 — keep the histogram pass.  SQLRS_RP_H2_UNPACKED=0: off)
-      const char *h2u_e = hook("SQLRS_RP_H2_UNPACKED");
-      const bool h2_unpacked = !pack && nv == 1 && ROWS == 12 && psrc != 3 && !(h2u_e && std::atoi(h2u_e) == 0) &&
+      //  buckets, C4 over general keys; 65 536 buckets — the sparse-key C5 — keep the histogram pass)
+      const bool h2_unpacked = !pack && nv == 1 && psrc != 3 &&
                                (size_t)RP_TILE * (8 * 2 + 4 + 2) + (size_t)WG * (4 + 4 + 8 + 8) + (size_t)WG * 8 + (size_t)P * 4 <= 159 * 1024;
-      const bool h2 = (pack || h2_unpacked) && nv == 1 && (ROWS == 12 || ROWS == 16) && ct_env == 1 && (size_t)P * 4 <= 24 * 1024 && !(h2_e && std::atoi(h2_e) == 0);
+      const bool h2 = (pack || h2_unpacked) && nv == 1 && (size_t)P * 4 <= 24 * 1024 && !(h2_e && std::atoi(h2_e) == 0);
       BufP chist = h2 ? ctx->alloc(4 * (size_t)max_chunks * ((size_t)1 << p2_bits)) : nullptr;
       co.hist = chist ? chist->as<uint32_t>() : nullptr;
       const size_t clds = (size_t)RP_TILE * (pack ? 8 * (1 + nv) : 8 * (1 + nv) + 4 + 2) + (size_t)WG * (4 + 4 + 8 + 8) +
@@ -746,7 +675,7 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
 #define SQ_CS1(NV, R, PK, PS)                                                                                       \
   do {                                                                                                              \
     auto kfn = rp_chunk_scatter_kernel<NV, 512, R, PK, PS>;                                                         \
-    if (NV == 1 && PK && (R == 12 || R == 16) && h2) kfn = rp_chunk_scatter_kernel<NV, 512, R, PK, PS, (NV == 1 && PK && (R == 12 || R == 16))>; \
+    if (NV == 1 && PK && h2) kfn = rp_chunk_scatter_kernel<NV, 512, R, PK, PS, (NV == 1 && PK)>;                    \
     allow_big_lds(ctx, kfn);                                                                                        \
     kfn<<<dim3(cwgs), dim3(512), clds, ctx->stream>>>(k, a0, a1, in.filter, n, co, P, p2_bits, d1, tiles1, ctpw,   \
                                                       sink, kp);                                                    \
@@ -758,11 +687,9 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
     else SQ_CS1(NV, R, PK, 3);                                                                                      \
   } while (0)
         if (nv == 2) SQ_CS(2, 8, false);
-        else if (ROWS == 16) SQ_CS(1, 16, true);
-        else if (ROWS != 12) { chunked = false; } // tuning shapes (SQLRS_RP_ROWS) keep the counting first level
         else if (nv == 0) { if (pack) SQ_CS(0, 12, true); else SQ_CS(0, 12, false); }
         // (768 threads x 8 rows for the unpacked rows of hashed partitions too: sparse-key C5 level 1 6.91 -> 6.81 ms in one process;
-        //  SQLRS_RP_L1G_WG=512, read per call, = the eight-wave form; a predicate on a column of its own keeps it: 14 spilled registers)
+        //  a predicate on a column of its own keeps the eight-wave form: 14 spilled registers)
         else if (!pack && h2) { // unpacked rows + the next level's counts: the 512-thread tile (the 768-thread one has no room for them)
 #define SQ_CH(PS)                                                                                                   \
   do {                                                                                                              \
@@ -773,7 +700,7 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
           if (psrc < 0) SQ_CH(-1); else SQ_CH(1);
 #undef SQ_CH
         }
-        else if (!pack && psrc != 3 && !(hook("SQLRS_RP_L1G_WG") && std::atoi(hook("SQLRS_RP_L1G_WG")) == 512)) {
+        else if (!pack && psrc != 3) {
           const size_t clds768 = (size_t)RP_TILE * (8 * (1 + nv) + 4 + 2) + (size_t)768 * (4 + 4 + 8 + 8) + (clds - ((size_t)RP_TILE * (8 * (1 + nv) + 4 + 2) + (size_t)WG * (4 + 4 + 8 + 8)));
 #define SQ_CG(PS)                                                                                                   \
   do {                                                                                                              \
@@ -784,67 +711,64 @@ bool partition_rows(Ctx *ctx, const PartitionInput &in, uint32_t P_wanted, Parti
           if (psrc < 0) SQ_CG(-1); else if (psrc == 1) SQ_CG(1); else SQ_CG(3);
 #undef SQ_CG
         }
-        else { if (pack) SQ_CS(1, 12, true); else SQ_CS(1, 12, false); }
+        else if (pack) SQ_CS(1, 12, true); else SQ_CS1(1, 12, false, 3);
 #undef SQ_CS
 #undef SQ_CS1
         SQ_HIP(hipGetLastError());
       }
-      if (!chunked && in.filter.col) return false;
-      if (chunked) {
-        // level-2 geometry from the chunk table, on the device; the host only needs three numbers
-        const uint32_t digits2 = 1u << p2_bits;
-        Level L2;
-        L2.nseg = d1;
-        const LevelLayout lay(d1);
-        L2.dev = ctx->alloc(lay.total);
-        bind_level(L2, lay);
-        L2.tiles = ctx->alloc(sizeof(Tile) * (size_t)max_chunks * (size_t)ct_env);
-        BufP totals = ctx->alloc(24);
-        BufP tile_chunk = h2 ? ctx->alloc(4 * (size_t)max_chunks) : nullptr;
-        BufP plan = ctx->alloc(sizeof(ChunkPlan));
-        SQ_HIP(hipMemsetAsync(plan->p, 0, sizeof(ChunkPlan), ctx->stream));
-        const unsigned pblocks = (unsigned)std::min<uint64_t>(ceil_div((int64_t)max_chunks, 256 * 8), 128);
-        rp_chunk_count_kernel<<<dim3(pblocks), dim3(256), 0, ctx->stream>>>(co.chunk_len, co.chunk_dig, co.counter, co.base_chunks,
-                                                                          co.max_chunks, (uint32_t)RP_TILE, plan->as<ChunkPlan>());
-        rp_chunk_prefix_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(
-            plan->as<ChunkPlan>(), co.counter, d1, digits2, (int64_t *)L2.d_seg_start, (int64_t *)L2.d_seg_mat,
-            (uint32_t *)L2.d_seg_tiles, (uint32_t *)L2.d_seg_tile_base, totals->as<uint64_t>());
-        rp_chunk_assign_kernel<<<dim3(pblocks), dim3(256), 0, ctx->stream>>>(
-            co.chunk_len, co.chunk_dig, co.counter, co.base_chunks, co.max_chunks, digits2, (uint32_t)CAP, (uint32_t)RP_TILE,
-            L2.d_seg_tiles, L2.d_seg_tile_base, plan->as<ChunkPlan>(), (Tile *)L2.tiles->p,
-            tile_chunk ? tile_chunk->as<uint32_t>() : nullptr);
+      // level-2 geometry from the chunk table, on the device; the host only needs three numbers
+      const uint32_t digits2 = 1u << p2_bits;
+      Level L2;
+      L2.nseg = d1;
+      const LevelLayout lay(d1);
+      L2.dev = ctx->alloc(lay.total);
+      bind_level(L2, lay);
+      L2.tiles = ctx->alloc(sizeof(Tile) * (size_t)max_chunks);
+      BufP totals = ctx->alloc(24);
+      BufP tile_chunk = h2 ? ctx->alloc(4 * (size_t)max_chunks) : nullptr;
+      BufP plan = ctx->alloc(sizeof(ChunkPlan));
+      SQ_HIP(hipMemsetAsync(plan->p, 0, sizeof(ChunkPlan), ctx->stream));
+      const unsigned pblocks = (unsigned)std::min<uint64_t>(ceil_div((int64_t)max_chunks, 256 * 8), 128);
+      rp_chunk_count_kernel<<<dim3(pblocks), dim3(256), 0, ctx->stream>>>(co.chunk_len, co.chunk_dig, co.counter, co.base_chunks,
+                                                                        co.max_chunks, (uint32_t)RP_TILE, plan->as<ChunkPlan>());
+      rp_chunk_prefix_kernel<<<dim3(1), dim3(64), 0, ctx->stream>>>(
+          plan->as<ChunkPlan>(), co.counter, d1, digits2, (int64_t *)L2.d_seg_start, (int64_t *)L2.d_seg_mat,
+          (uint32_t *)L2.d_seg_tiles, (uint32_t *)L2.d_seg_tile_base, totals->as<uint64_t>());
+      rp_chunk_assign_kernel<<<dim3(pblocks), dim3(256), 0, ctx->stream>>>(
+          co.chunk_len, co.chunk_dig, co.counter, co.base_chunks, co.max_chunks, digits2, (uint32_t)CAP, (uint32_t)RP_TILE,
+          L2.d_seg_tiles, L2.d_seg_tile_base, plan->as<ChunkPlan>(), (Tile *)L2.tiles->p,
+          tile_chunk ? tile_chunk->as<uint32_t>() : nullptr);
+      SQ_HIP(hipGetLastError());
+      const uint64_t *ht = (const uint64_t *)ctx->fetch(totals->p, 24);
+      const uint64_t ntiles = ht[0], kept = ht[1], overflow = ht[2];
+      if (overflow) return false; // (impossible by the chunk bound; never trusted blindly)
+      L2.num_tiles = (uint32_t)ntiles;
+      L2.mat_entries = (int64_t)ntiles * digits2;
+      out->n = (int64_t)kept;
+      out->P = P;
+      RpIn rin2;
+      rin2.key = ck->as<uint64_t>();
+      rin2.v0 = co.v0;
+      rin2.v1 = co.v1;
+      rin2.idx = co.idx;
+      rin2.flags = nullptr;
+      rin2.key_validity = rin2.v0_validity = rin2.v1_validity = nullptr;
+      Cols c2;
+      RpOut rout2;
+      alloc_cols((int64_t)kept, true, c2, rout2);
+      BufP offs2, premat;
+      if (h2 && L2.mat_entries) { // the level's count matrix is already known: no histogram pass over the chunks
+        premat = ctx->alloc(4 * (size_t)L2.mat_entries);
+        rp_hist_from_chunks_kernel<<<dim3((unsigned)ceil_div(L2.mat_entries, 256)), dim3(256), 0, ctx->stream>>>(
+            co.hist, tile_chunk->as<uint32_t>(), L2.mat_entries, digits2, premat->as<uint32_t>());
         SQ_HIP(hipGetLastError());
-        const uint64_t *ht = (const uint64_t *)ctx->fetch(totals->p, 24);
-        const uint64_t ntiles = ht[0], kept = ht[1], overflow = ht[2];
-        if (overflow) return false; // (impossible by the chunk bound; never trusted blindly)
-        L2.num_tiles = (uint32_t)ntiles;
-        L2.mat_entries = (int64_t)ntiles * digits2;
-        out->n = (int64_t)kept;
-        out->P = P;
-        RpIn rin2;
-        rin2.key = ck->as<uint64_t>();
-        rin2.v0 = co.v0;
-        rin2.v1 = co.v1;
-        rin2.idx = co.idx;
-        rin2.flags = nullptr;
-        rin2.key_validity = rin2.v0_validity = rin2.v1_validity = nullptr;
-        Cols c2;
-        RpOut rout2;
-        alloc_cols((int64_t)kept, true, c2, rout2);
-        BufP offs2, premat;
-        if (h2 && L2.mat_entries) { // the level's count matrix is already known: no histogram pass over the chunks
-          premat = ctx->alloc(4 * (size_t)L2.mat_entries);
-          rp_hist_from_chunks_kernel<<<dim3((unsigned)ceil_div(L2.mat_entries, 256)), dim3(256), 0, ctx->stream>>>(
-              co.hist, tile_chunk->as<uint32_t>(), L2.mat_entries, digits2, premat->as<uint32_t>());
-          SQ_HIP(hipGetLastError());
-        }
-        EarlyStarts es;
-        early_starts_for(L2, digits2, (int64_t)kept, es);
-        exec_level(2, digits2, L2, rin2, rout2, (int64_t)kept, &offs2, premat, nullptr, &es.queue);
-        publish(c2);
-        out->bstart = finish_starts(es, L2, offs2, digits2, (int64_t)kept, &out->bstart_host);
-        return true;
       }
+      EarlyStarts es;
+      early_starts_for(L2, digits2, (int64_t)kept, es);
+      exec_level(2, digits2, L2, rin2, rout2, (int64_t)kept, &offs2, premat, nullptr, &es.queue);
+      publish(c2);
+      out->bstart = finish_starts(es, L2, offs2, digits2, (int64_t)kept, &out->bstart_host);
+      return true;
     }
   }
 

@@ -191,7 +191,7 @@ __device__ __forceinline__ void rp_load_tile(const RpIn &in, const Tile &t, uint
 // LDS phases (rank with LDS atomics -> scan -> stage sorted -> coalesced stores), which hides the
 // HBM latency that a 150 KiB-LDS kernel (one workgroup per CU) cannot hide with occupancy.
 template <int NV, int RP_WG, int RP_ROWS, int MODE, bool PACK, bool REC = false>
-__global__ __launch_bounds__(RP_WG, (RP_ROWS <= 6 || (PACK && RP_ROWS <= 8 && NV <= 1)) ? 2 : 1) void rp_scatter_kernel(RpIn in, RpOut out,
+__global__ __launch_bounds__(RP_WG, 1) void rp_scatter_kernel(RpIn in, RpOut out,
                                                            const Tile *__restrict__ tiles, uint32_t P,
                                                            uint32_t p2_bits, int level, uint32_t digits,
                                                            const uint32_t *__restrict__ offs,
@@ -943,13 +943,12 @@ __device__ __forceinline__ void rp_slim_load(const SlimIn &in, const Tile &t, ui
   r.cs1 = cs[64 + lane_id()];
 }
 
-template <int RP_WG, int RP_ROWS>
-__global__ __launch_bounds__(RP_WG, 1) void rp_scatter_slim_kernel(SlimIn in, SlimOut out, const Tile *__restrict__ tiles,
-                                                                  uint32_t p2_bits, uint32_t digits,
-                                                                  const uint32_t *__restrict__ offs, uint32_t num_tiles,
-                                                                  uint32_t tiles_per_wg, int64_t sink, uint32_t kshift,
-                                                                  uint32_t rbits) {
-  constexpr int RP_TILE = RP_WG * RP_ROWS;
+__global__ __launch_bounds__(512, 1) void rp_scatter_slim_kernel(SlimIn in, SlimOut out, const Tile *__restrict__ tiles,
+                                                                uint32_t p2_bits, uint32_t digits,
+                                                                const uint32_t *__restrict__ offs, uint32_t num_tiles,
+                                                                uint32_t tiles_per_wg, int64_t sink, uint32_t kshift,
+                                                                uint32_t rbits) {
+  constexpr int RP_WG = 512, RP_ROWS = 12, RP_TILE = RP_WG * RP_ROWS;
   static_assert(SLIM_RUNS == 128 && RP_TILE / 64 <= 128, "one mask word per 64 positions of a chunk");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint64_t *sv0 = (uint64_t *)smem;

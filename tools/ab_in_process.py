@@ -27,7 +27,7 @@ print("ptrs", hex(fk.data_ptr()), hex(fv.data_ptr()))
 pipe = bench.Pipeline(be, abi, 0.5, fused=os.environ.get("UNFUSED") != "1")  # UNFUSED=1: Filter, HashJoin, HashAgg as three operators
 def step():
     pipe.step(bench.device_batch(abi, [dk], [abi.INT64]), bench.device_batch(abi, [fk, fv], [abi.INT64, abi.FLOAT64])).release()
-VAR = os.environ.get("VAR", "SQLRS_RP_CHUNK_TILES")  # a hook the library reads per call
+VAR = os.environ.get("VAR", "SQLRS_RP_CONC")  # a hook the library reads per call
 for rep in range(int(os.environ.get("REPS", 3))):
     if os.environ.get("TRIM"):  # fresh pool blocks every round: the variants are compared over several placements
         be.fn("ctx_pool_trim")(be.ctx)
