@@ -525,8 +525,8 @@ int sqlrs_batch_to_string(sqlrs_ctx_t *ctx, const sqlrs_batch_t *in, char **out)
 void sqlrs_string_free(char *s);
 
 /* CSV ingest [ref: src/storage/csv.rs:92-106 CsvConfig (header, ',', infer over 10 records, batches of
- * 1024 rows), :124-133 schema inference, :190-241 CsvTransaction::next_batch].  Parsed on the host; with
- * out_mem = SQLRS_MEM_DEVICE every batch is uploaded once and the scan's output is HBM resident.
+ * 1024 rows), :124-133 schema inference, :190-241 CsvTransaction::next_batch].  Parsed on the host (on the device after
+ * sqlrs_csv_set_device_parse); with out_mem = SQLRS_MEM_DEVICE the scan's output is HBM resident.
  * Inferred types: INT64, FLOAT64, BOOLEAN, else UTF8 (date-like columns stay UTF8: the path has no date
  * type); a missing value is NULL in a typed column and the empty string in a UTF8 column. */
 typedef struct sqlrs_csv sqlrs_csv_t;
@@ -544,6 +544,26 @@ int sqlrs_csv_set_projection(sqlrs_csv_t *r, int num_columns, const int32_t *col
 /* *out = NULL at the end of the scan */
 int sqlrs_csv_next_batch(sqlrs_csv_t *r, int out_mem, sqlrs_batch_t **out);
 void sqlrs_csv_close(sqlrs_csv_t *r);
+/* The device form of the scan: the bytes -> columns work of sqlrs_csv_next_batch done by gfx950 kernels (csv_device.hip).
+ * chunk_bytes = 0: host parser (the default); > 0: parse on the device, the file read in pieces of this many bytes (at most
+ * 2^31 - 65); < 0: on, with the library's piece size (32 MiB).  Call before the first sqlrs_csv_next_batch.
+ * Contract: the sequence of sqlrs_csv_next_batch results — number of batches, rows per batch, dtypes, values bit for bit,
+ * validity, Utf8 offsets and bytes, *out = NULL at the end, and for bad input the status, the sqlrs_last_error text and the
+ * batch at which it is raised (every earlier batch still delivered) — is the host parser's for the same file, bounds,
+ * projection, batch_size, has_header, delimiter and out_mem.  That is: records end at '\n', one trailing '\r' is stripped,
+ * a line that is empty after that is skipped, a last record without '\n' counts, the delimiter is any single byte; an empty
+ * field is the empty string in a Utf8 column and NULL in a typed one; Int64 and Float64 are std::from_chars (Float64 in
+ * general format, correctly rounded; "inf", "nan", "1e+5", "1.", ".5" are read), Boolean is true / false in any case; a
+ * record with another field count than the schema and an unparsable typed field are SQLRS_ERR_ARROW with the host parser's
+ * text and line number.
+ * What the device does not decide it hands back, and counts: a piece with a '"' byte anywhere, a record longer than a piece
+ * and the batch in which the device met an error are read by the host parser (whole batches, from the first record of the
+ * batch under construction: host_rows); a Float64 field that is not -?digits[.digits][(e|E)[-]digits] with fewer than 2^53
+ * as its digits and a decimal exponent within +-22 — where one IEEE multiply or divide of two exact doubles is the correctly
+ * rounded value — is written by the host with std::from_chars (patched_fields).  More than 32 projected columns: host parser. */
+int sqlrs_csv_set_device_parse(sqlrs_csv_t *r, int64_t chunk_bytes);
+/* rows delivered by the device parser / by the host parser since the switch was set / typed fields the device left to the host */
+int sqlrs_csv_device_stats(const sqlrs_csv_t *r, int64_t *device_rows, int64_t *host_rows, int64_t *patched_fields);
 
 /* --------------------------------------------------------------- exchange -- */
 /* Hash-partitions a batch on one key expression for the multi-GPU partitioned join /

@@ -449,6 +449,8 @@ class Backend:
             "csv_set_projection": (i, [vp, i, C.POINTER(C.c_int32)]),
             "csv_next_batch": (i, [vp, i, ppb]),
             "csv_close": (None, [vp]),
+            "csv_set_device_parse": (i, [vp, C.c_int64]),
+            "csv_device_stats": (i, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
             "timer_create": (i, [vp, pvp]),
             "timer_start": (i, [vp]),
             "timer_stop": (i, [vp]),

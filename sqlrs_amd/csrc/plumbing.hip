@@ -11,6 +11,7 @@
 #include <strings.h>
 
 #include "common.hpp"
+#include "csv_reader.hpp"
 #include "host_stage.hpp"
 #include "device_utils.hpp"
 #include "prims.hpp"
@@ -179,19 +180,6 @@ bool read_record(std::istream &in, char delim, std::vector<std::string> &fields)
 }
 
 } // namespace
-
-struct sqlrs_csv {
-  Ctx *ctx = nullptr;
-  std::ifstream file;
-  char delimiter = ',';
-  int64_t batch_size = 1024;
-  std::vector<std::string> names;
-  std::vector<int32_t> dtypes;
-  std::vector<int> projection; // indices into the file's columns
-  uint64_t remaining = ~0ull;  // records still allowed by the bounds
-  uint64_t line = 0;           // for error messages
-  bool has_header = true;
-};
 
 extern "C" {
 
@@ -874,6 +862,17 @@ int sqlrs_csv_set_projection(sqlrs_csv_t *r, int num_columns, const int32_t *col
 // next batch of <= batch_size records, *out = NULL at the end of the scan [ref: csv.rs:236-241]
 int sqlrs_csv_next_batch(sqlrs_csv_t *r, int out_mem, sqlrs_batch_t **out) {
   return guard(r->ctx, [&] {
+    if (r->dev) csv_device_next_batch(r, out_mem, out);
+    else csv_host_next_batch(r, out_mem, out);
+  });
+}
+void sqlrs_csv_close(sqlrs_csv_t *r) { delete r; }
+
+} // extern "C"
+
+// the host parser: the specification of the reader (the device parser of csv_device.hip returns its stream of batches)
+void sq::csv_host_next_batch(sqlrs_csv *r, int out_mem, sqlrs_batch_t **out) {
+  {
     Ctx *ctx = r->ctx;
     *out = nullptr;
     const size_t nc = r->projection.size();
@@ -969,8 +968,5 @@ int sqlrs_csv_next_batch(sqlrs_csv_t *r, int out_mem, sqlrs_batch_t **out) {
     ctx->sync(); // the uploads read the host blocks
     sqlrs_batch_release(host);
     *out = dev;
-  });
+  }
 }
-void sqlrs_csv_close(sqlrs_csv_t *r) { delete r; }
-
-} // extern "C"
