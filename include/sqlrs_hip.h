@@ -724,6 +724,10 @@ int sqlrs_ctx_profile_reset(sqlrs_ctx_t *ctx);
 int sqlrs_ctx_profile_read(sqlrs_ctx_t *ctx, int cap, const char **names, double *total_ms,
                            int64_t *launches);
 
+/* Rows one workgroup of the fused `col OP const` filter takes at a time (its tile): the row counts around which that
+ * kernel changes shape — for tests that must straddle it. */
+int64_t sqlrs_filter_tile_rows(void);
+
 /* Library version string ("sqlrs-hip <semver> gfx950"). */
 const char *sqlrs_version(void);
 

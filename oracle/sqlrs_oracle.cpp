@@ -439,8 +439,10 @@ Col cast(const Col &in, int32_t to) {
       }
       o.i = s.i;
     } else if ((to == SQLRS_INT64 || to == SQLRS_INT32) && from_f) {
+      // in range = the truncated value fits: (-2^31 - 1, 2^31) for int32; [-2^63, 2^63) for int64, where -2^63 - 1 is
+      // not a double (it rounds to -2^63, which IS INT64_MIN) and the lower bound is therefore inclusive
       double lim = to == SQLRS_INT32 ? 2147483648.0 : 9223372036854775808.0;
-      if (!(s.f > -lim - 1 && s.f < lim)) {
+      if (!((to == SQLRS_INT32 ? s.f > -lim - 1 : s.f >= -lim) && s.f < lim)) {
         b.append_null();
         continue;
       }

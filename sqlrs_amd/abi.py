@@ -458,6 +458,7 @@ class Backend:
             "timer_destroy": (None, [vp]),
             "ctx_profile_enable": (i, [vp, i]),
             "ctx_profile_reset": (i, [vp]),
+            "filter_tile_rows": (C.c_int64, []),
             "ctx_profile_read": (i, [vp, i, C.POINTER(C.c_char_p), C.POINTER(C.c_double),
                                      C.POINTER(C.c_int64)]),
         }

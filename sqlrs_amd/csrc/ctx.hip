@@ -1242,6 +1242,14 @@ int sqlrs_ctx_profile_read(sqlrs_ctx_t *ctx, int cap, const char **names, double
     }
     n++;
   }
+  if (ctx->async_conj_batches) { // (a count: the async_fast_batches that were `col OP const [AND ...]` filters, evaluated without the program)
+    if (n < cap) {
+      names[n] = "async_conj_batches";
+      total_ms[n] = 0;
+      launches[n] = ctx->async_conj_batches;
+    }
+    n++;
+  }
   if (ctx->order_lb_fallbacks) { // (advisor r05: the process-wide switch-off of the Order look-back is visible, tests/conftest.py checks it)
     if (n < cap) {
       names[n] = "order_lookback_fallbacks";

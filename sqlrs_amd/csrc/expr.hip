@@ -143,8 +143,9 @@ __global__ __launch_bounds__(BLOCK) void cast_kernel(const S *__restrict__ in, i
   if (i < n) {
     S v = in[i];
     if constexpr (std::is_floating_point<S>::value && !std::is_floating_point<D>::value) {
+      // (-2^31 - 1, 2^31) for int32; [-2^63, 2^63) for int64: -2^63 - 1 rounds to -2^63, which is INT64_MIN itself
       double lim = sizeof(D) == 4 ? 2147483648.0 : 9223372036854775808.0;
-      ok = (v > -lim - 1) && (v < lim);
+      ok = (sizeof(D) == 4 ? v > -lim - 1 : v >= -lim) && (v < lim);
       out[i] = ok ? (D)v : D(0);
     } else if constexpr (sizeof(D) < sizeof(S) && !std::is_floating_point<D>::value) {
       ok = (v <= (S)INT32_MAX) && (v >= (S)INT32_MIN);

@@ -296,7 +296,7 @@ __global__ __launch_bounds__(1024) void sa_filter_kernel(SaGroup<SaFilterParams>
     }
     if (valid) sa_pack_validity(s_v, total, p.out + col.out_voff, &s_nulls[c]);
   }
-  sa_publish((SaHeader *)p.out, p.seq, total, s_nulls, p.lay.ncols, s_div0);
+  sa_publish((SaHeader *)p.out, p.seq, total, s_nulls, p.lay.ncols, &s_div0);
 }
 static void sa_filter_launch(SaRing *r, Ctx *ctx) {
   SaGroup<SaFilterParams> g;
@@ -370,6 +370,7 @@ int sqlrs_filter_push_async(sqlrs_filter_t *f, const sqlrs_batch_t *in, sqlrs_ti
           p.out = r->out_area(slot);
           p.seq = ++r->seq;
           sa_enqueue(ctx, r, f, sa_filter_launch, p, slot);
+          if (p.nterms) ctx->async_conj_batches++; // (sa_filter_shape took it: the program counts in async_fast_batches alone)
           t->slot = slot;
           t->seq = p.seq;
           t->lay = p.lay;

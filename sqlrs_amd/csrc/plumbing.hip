@@ -289,7 +289,7 @@ __global__ __launch_bounds__(1024) void sa_project_kernel(SaGroup<SaProjectParam
       }
     }
   }
-  sa_publish((SaHeader *)p.out, p.seq, rows, s_nulls, p.nout, s_div0);
+  sa_publish((SaHeader *)p.out, p.seq, rows, s_nulls, p.nout, &s_div0);
 }
 static void sa_project_launch(SaRing *r, Ctx *ctx) {
   SaGroup<SaProjectParams> g;

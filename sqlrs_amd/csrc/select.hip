@@ -316,7 +316,7 @@ constexpr int FILTER_WAVES = FILTER_WAVES_N; // even: two worker waves per 4096-
 #define FILTER_CHUNKS_N 32
 #endif
 constexpr int FILTER_CHUNKS = FILTER_CHUNKS_N;                   // 64-row chunks per worker wave
-constexpr int FILTER_TILE_ROWS = FILTER_WAVES * FILTER_CHUNKS * 64; // 16384
+constexpr int FILTER_TILE_ROWS = FILTER_WAVES * FILTER_CHUNKS * 64; // 20480 (sqlrs_filter_tile_rows)
 constexpr int FILTER_SUB = FILTER_TILE_ROWS / TILE_ROWS;           // 4096-row tiles per filter tile
 constexpr int FILTER_BLOCK = (FILTER_WAVES + 1) * 64;
 constexpr int FILTER_WPS = TILE_ROWS / (FILTER_CHUNKS * 64);      // worker waves per 4096-row compaction tile
@@ -649,3 +649,5 @@ bool filter_fast_path(Ctx *ctx, const Expr &e, const std::function<const DCol &(
 }
 
 } // namespace sq
+
+extern "C" int64_t sqlrs_filter_tile_rows(void) { return sq::FILTER_TILE_ROWS; }

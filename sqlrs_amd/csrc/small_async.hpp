@@ -175,7 +175,7 @@ __device__ __forceinline__ unsigned long long sa_eval_row(const SaProgram &pr, c
       } else { // float64 -> integer
         const double f = __longlong_as_double((long long)x);
         const double lim = I.dtype == SQLRS_INT32 ? 2147483648.0 : 9223372036854775808.0;
-        const bool in_range = (f > -lim - 1) && (f < lim);
+        const bool in_range = (I.dtype == SQLRS_INT32 ? f > -lim - 1 : f >= -lim) && (f < lim); // (-2^63 is INT64_MIN: inclusive, expr.hip cast_kernel)
         x = in_range ? (I.dtype == SQLRS_INT32 ? (unsigned long long)(long long)(int32_t)f : (unsigned long long)(long long)f) : 0ull;
         o = o && in_range;
       }
@@ -291,14 +291,16 @@ __device__ __forceinline__ void sa_pack_validity(const uint8_t *s_v, uint32_t to
   __syncthreads();
 }
 // the last step of a fast-path kernel: every thread's stores to the pinned output are pushed out, then ONE thread
-// publishes the header
+// publishes the header.  `s_error` (LDS, may be null) is read BEHIND the barrier like `s_nulls`: any wave may have raised it
+// last (passed by value it was thread 0's view in front of the barrier, and a division by zero seen by another wave of the
+// Project kernel, which has no barrier of its own after the rows, could be lost)
 __device__ __forceinline__ void sa_publish(SaHeader *hdr, unsigned long long seq, uint32_t total, const uint32_t *s_nulls, int ncols,
-                                           uint32_t error = 0) {
+                                           const uint32_t *s_error = nullptr) {
   __threadfence_system();
   __syncthreads();
   if (threadIdx.x == 0) {
     hdr->count = total;
-    hdr->pad = error; // (1: a valid row divided by zero — sqlrs_batch_wait turns it into the evaluator's Arrow error)
+    hdr->pad = s_error ? *s_error : 0u; // (1: a valid row divided by zero — sqlrs_batch_wait turns it into the evaluator's Arrow error)
     for (int c = 0; c < ncols; c++) hdr->nulls[c] = s_nulls[c];
     __threadfence_system();
     __hip_atomic_store(&hdr->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
