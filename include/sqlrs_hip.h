@@ -562,6 +562,20 @@ void sqlrs_csv_close(sqlrs_csv_t *r);
  * as its digits and a decimal exponent within +-22 — where one IEEE multiply or divide of two exact doubles is the correctly
  * rounded value — is written by the host with std::from_chars (patched_fields).  More than 32 projected columns: host parser. */
 int sqlrs_csv_set_device_parse(sqlrs_csv_t *r, int64_t chunk_bytes);
+/* on != 0: pieces that contain '"' bytes are parsed on the device too, as long as every quote in the piece is regular
+ * (below); any other piece is handed back exactly as without the switch.  Needs sqlrs_csv_set_device_parse; either order;
+ * before the first sqlrs_csv_next_batch (later: SQLRS_ERR_INTERNAL).  Default 0.  The contract of
+ * sqlrs_csv_set_device_parse holds unchanged: the stream of batches is the host parser's, errors included.
+ * With every '"' toggling "inside quotes" from the start of a piece (a piece starts at a record's start, outside), a quote
+ * that opens is regular iff it is the piece's first byte or follows the delimiter, a '\n' or a quote (which then closed:
+ * the "" of an escaped quote); a quote that closes is regular iff the delimiter, '\n', "\r\n" or a quote follows.  Then the
+ * separators are the delimiters and record-ending '\n' outside quotes, a field that starts with '"' also ends in one, and
+ * its value is what lies between them with "" read as '"' (a typed field: parsed from that; "" is NULL).  A piece is cut at
+ * its last '\n' outside quotes.  Handed back (host_rows): a piece with an irregular quote in front of that cut — a quote in
+ * the middle of an unquoted field, text behind a closing quote, "x"\r followed by the delimiter — a piece without such a cut
+ * (a record longer than a piece, also through quoted line breaks; a quote left open at the end of the file), and, as ever,
+ * the batch with an error.  A delimiter that is '"', '\n' or '\r' leaves the switch without effect. */
+int sqlrs_csv_set_device_quotes(sqlrs_csv_t *r, int on);
 /* rows delivered by the device parser / by the host parser since the switch was set / typed fields the device left to the host */
 int sqlrs_csv_device_stats(const sqlrs_csv_t *r, int64_t *device_rows, int64_t *host_rows, int64_t *patched_fields);
 

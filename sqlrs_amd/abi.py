@@ -450,6 +450,7 @@ class Backend:
             "csv_next_batch": (i, [vp, i, ppb]),
             "csv_close": (None, [vp]),
             "csv_set_device_parse": (i, [vp, C.c_int64]),
+            "csv_set_device_quotes": (i, [vp, C.c_int]),
             "csv_device_stats": (i, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
             "timer_create": (i, [vp, pvp]),
             "timer_start": (i, [vp]),

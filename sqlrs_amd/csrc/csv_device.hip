@@ -3,13 +3,15 @@
 // hands out batch_size rows at a time, cut from what the pieces produced (a batch may span pieces, a piece many batches).
 //
 // The host parser (plumbing.hip) is the specification, and the fallback at two granularities:
-//   * a piece with a '"' byte, a record longer than a piece, and the batch in which the device found an error are read by
-//     the host parser: the file is positioned at the first record of the batch under construction and whole batches are
-//     parsed there until the file position is behind the piece (an error: the host parser raises its own message, and
-//     the reader stays with it) — the stream of batches is the host parser's by construction;
+//   * a piece with a '"' byte (sqlrs_csv_set_device_quotes: a piece with an irregular quote in front of its last record
+//     end), a record longer than a piece, and the batch in which the device found an error are read by the host parser:
+//     the file is positioned at the first record of the batch under construction and whole batches are parsed there
+//     until the file position is behind the piece (an error: the host parser raises its own message, and the reader
+//     stays with it) — the stream of batches is the host parser's by construction;
 //   * a Float64 field outside csv_parse_float64's exactly rounded rule is written by std::from_chars (the patch list).
-// Two host round trips per piece: (separators, first ragged row, quote flag), then (error row, patch list, NULLs and Utf8
-// bytes per output batch, where the trailing batch starts); none per batch.
+// With sqlrs_csv_set_device_quotes a piece is cut at its last '\n' outside quotes, which the device reports.
+// Two host round trips per piece: (separators, first ragged row, quote flag / first irregular quote and the cut), then
+// (error row, patch list, NULLs and Utf8 bytes per output batch, where the trailing batch starts); none per batch.
 #include <algorithm>
 #include <charconv>
 
@@ -32,7 +34,7 @@ struct CsvDevice {
   uint8_t *ctl_pin = nullptr;     // control words up, counts and lists down
   size_t ctl_cap = 0;
   // ---- the piece in HBM
-  BufP bytes, sep_pos, tile_cnt, tile_off, total, ctl, seg_stats, patches, patch_vals, vb;
+  BufP bytes, sep_pos, tile_cnt, tile_off, tile_quotes, tile_qoff, total, ctl, seg_stats, patches, patch_vals, vb;
   struct Slot {
     BufP val, flag, ustart, ulen, uoff;
   };
@@ -40,6 +42,7 @@ struct CsvDevice {
   CsvParams P;
   int64_t piece_pos = 0, piece_rows = 0, piece_next = 0, nseg = 0, tail_start_off = 0;
   bool piece_trouble = false; // the row behind piece_rows is one the host parser has to look at
+  bool piece_quotes = false;  // parsed by the quote-aware kernels
   std::vector<uint32_t> seg_nulls, seg_bytes;
   // ---- the batch under construction
   struct Col {
@@ -156,28 +159,61 @@ void load_piece(sqlrs_csv *r, CsvDevice &d) {
   need(ctx, d.ctl, sizeof(CsvCtl));
   const uint8_t *bytes = d.bytes->as<uint8_t>();
   CsvCtl *ctl = d.ctl->as<CsvCtl>();
-  *(CsvCtl *)d.ctl_pin = CsvCtl{0, CSV_NO_ROW, CSV_NO_ROW, 0};
+  *(CsvCtl *)d.ctl_pin = CsvCtl{0, CSV_NO_ROW, CSV_NO_ROW, 0, CSV_NO_ROW, 0, 0, 0};
+  // (a delimiter that is a quote or a line end's byte: the quote rule is not stated for it)
+  const bool Q = d.piece_quotes = r->device_quotes && r->delimiter != '"' && r->delimiter != '\n' && r->delimiter != '\r';
   SQ_HIP(hipMemcpyAsync(d.bytes->p, d.pin, (size_t)len, hipMemcpyHostToDevice, ctx->stream));
   SQ_HIP(hipMemcpyAsync(ctl, d.ctl_pin, sizeof(CsvCtl), hipMemcpyHostToDevice, ctx->stream));
-  {
-    ProfScope ps(ctx, "csv_classify");
-    csv_classify_kernel<<<dim3((unsigned)ntiles), dim3(CSV_WG), 0, ctx->stream>>>(bytes, len, (uint8_t)r->delimiter,
-                                                                                 d.tile_cnt->as<uint32_t>(), ctl);
-  }
-  exclusive_scan_u32(ctx, d.tile_cnt->as<uint32_t>(), ntiles, nullptr, d.tile_off->as<uint32_t>(), d.total->as<uint64_t>());
-  {
-    ProfScope ps(ctx, "csv_index");
-    csv_index_kernel<<<dim3((unsigned)ntiles), dim3(CSV_WG), 0, ctx->stream>>>(bytes, len, (uint8_t)r->delimiter, (uint32_t)C,
-                                                                              d.tile_off->as<uint32_t>(), d.sep_pos->as<uint32_t>(), ctl);
+  if (Q) { // the parity pass runs whether the piece has quotes or not: no round trip to find out
+    need(ctx, d.tile_quotes, 4 * (size_t)ntiles);
+    need(ctx, d.tile_qoff, 4 * (size_t)ntiles);
+    const uint32_t *qoff = d.tile_qoff->as<uint32_t>();
+    {
+      ProfScope ps(ctx, "csv_quotes");
+      csv_quotes_kernel<<<dim3((unsigned)ntiles), dim3(CSV_WG), 0, ctx->stream>>>(bytes, len, d.tile_quotes->as<uint32_t>());
+    }
+    exclusive_scan_u32(ctx, d.tile_quotes->as<uint32_t>(), ntiles, nullptr, d.tile_qoff->as<uint32_t>(), d.total->as<uint64_t>());
+    {
+      ProfScope ps(ctx, "csv_classify_q");
+      csv_classify_q_kernel<<<dim3((unsigned)ntiles), dim3(CSV_WG), 0, ctx->stream>>>(bytes, len, (uint8_t)r->delimiter, qoff,
+                                                                                     d.tile_cnt->as<uint32_t>());
+    }
+    exclusive_scan_u32(ctx, d.tile_cnt->as<uint32_t>(), ntiles, nullptr, d.tile_off->as<uint32_t>(), d.total->as<uint64_t>());
+    {
+      ProfScope ps(ctx, "csv_index_q");
+      csv_index_q_kernel<<<dim3((unsigned)ntiles), dim3(CSV_WG), 0, ctx->stream>>>(
+          bytes, len, (uint8_t)r->delimiter, (uint32_t)C, qoff, d.tile_off->as<uint32_t>(), d.sep_pos->as<uint32_t>(), ctl);
+    }
+  } else {
+    {
+      ProfScope ps(ctx, "csv_classify");
+      csv_classify_kernel<<<dim3((unsigned)ntiles), dim3(CSV_WG), 0, ctx->stream>>>(bytes, len, (uint8_t)r->delimiter,
+                                                                                   d.tile_cnt->as<uint32_t>(), ctl);
+    }
+    exclusive_scan_u32(ctx, d.tile_cnt->as<uint32_t>(), ntiles, nullptr, d.tile_off->as<uint32_t>(), d.total->as<uint64_t>());
+    {
+      ProfScope ps(ctx, "csv_index");
+      csv_index_kernel<<<dim3((unsigned)ntiles), dim3(CSV_WG), 0, ctx->stream>>>(bytes, len, (uint8_t)r->delimiter, (uint32_t)C,
+                                                                                d.tile_off->as<uint32_t>(), d.sep_pos->as<uint32_t>(), ctl);
+    }
   }
   SQ_HIP(hipGetLastError());
   uint8_t *down = d.ctl_pin + CTL_DOWN;
   SQ_HIP(hipMemcpyAsync(down, ctl, sizeof(CsvCtl), hipMemcpyDeviceToHost, ctx->stream));
-  SQ_HIP(hipMemcpyAsync(down + 16, d.total->p, 8, hipMemcpyDeviceToHost, ctx->stream));
+  SQ_HIP(hipMemcpyAsync(down + 32, d.total->p, 8, hipMemcpyDeviceToHost, ctx->stream));
   ctx->sync();
   CsvCtl c = *(const CsvCtl *)down;
-  const uint64_t nsep = *(const uint64_t *)(down + 16);
+  uint64_t nsep = *(const uint64_t *)(down + 32);
   if (c.quote) return rewind_to_host(r, d, d.piece_pos, d.piece_pos + consumed);
+  if (Q) {
+    // the cut: the last record end outside quotes.  None: a record longer than the piece.  What lies behind it is the next
+    // piece's, its separators (ranks >= nsep) and quotes included
+    if (c.last_end_pos == 0) return rewind_to_host(r, d, d.piece_pos, d.piece_pos + n);
+    consumed = std::min(n, (int64_t)c.last_end_pos + 1);
+    if (c.bad_quote < c.last_end_pos) return rewind_to_host(r, d, d.piece_pos, d.piece_pos + consumed);
+    nsep = (uint64_t)c.last_end_rank + 1;
+    if (c.first_bad != CSV_NO_ROW && (uint64_t)c.first_bad * (uint64_t)C >= nsep) c.first_bad = CSV_NO_ROW;
+  }
   int64_t R = c.first_bad != CSV_NO_ROW ? (int64_t)c.first_bad : (int64_t)(nsep / (uint64_t)C);
   bool trouble = c.first_bad != CSV_NO_ROW;
   if ((uint64_t)R >= r->remaining) { // the bounds end the scan before the ragged record is read
@@ -225,8 +261,10 @@ void load_piece(sqlrs_csv *r, CsvDevice &d) {
     if (nfloat) need(ctx, d.patches, sizeof(CsvPatch) * (size_t)R * (size_t)nfloat);
     {
       ProfScope ps(ctx, "csv_parse");
-      csv_parse_kernel<<<dim3((unsigned)ceil_div(R + 1, CSV_WG), (unsigned)nslots), dim3(CSV_WG), 0, ctx->stream>>>(
-          bytes, d.sep_pos->as<uint32_t>(), P, seg_nulls, nfloat ? d.patches->as<CsvPatch>() : nullptr, ctl);
+      const dim3 grid((unsigned)ceil_div(R + 1, CSV_WG), (unsigned)nslots);
+      CsvPatch *patches = nfloat ? d.patches->as<CsvPatch>() : nullptr;
+      if (Q) csv_parse_kernel<true><<<grid, dim3(CSV_WG), 0, ctx->stream>>>(bytes, d.sep_pos->as<uint32_t>(), P, seg_nulls, patches, ctl);
+      else csv_parse_kernel<false><<<grid, dim3(CSV_WG), 0, ctx->stream>>>(bytes, d.sep_pos->as<uint32_t>(), P, seg_nulls, patches, ctl);
     }
     for (int s = 0; s < nslots; s++)
       if (P.slot[s].dtype == SQLRS_UTF8)
@@ -236,17 +274,17 @@ void load_piece(sqlrs_csv *r, CsvDevice &d) {
       csv_seg_bytes_kernel<<<dim3((unsigned)ceil_div(d.nseg, 256), (unsigned)nslots), dim3(256), 0, ctx->stream>>>(P, d.nseg, seg_bytes);
     }
     SQ_HIP(hipGetLastError());
-    need_ctl(ctx, d, CTL_DOWN + 32 + 4 * nstat_dev);
+    need_ctl(ctx, d, CTL_DOWN + 48 + 4 * nstat_dev);
     down = d.ctl_pin + CTL_DOWN;
     SQ_HIP(hipMemcpyAsync(down, ctl, sizeof(CsvCtl), hipMemcpyDeviceToHost, ctx->stream));
     const int64_t a_last = d.nseg > 1 ? P.seg_first + (d.nseg - 2) * B : 0; // where the piece's last batch starts
     if (a_last > 0)
-      SQ_HIP(hipMemcpyAsync(down + 16, d.sep_pos->as<uint32_t>() + a_last * C - 1, 4, hipMemcpyDeviceToHost, ctx->stream));
-    SQ_HIP(hipMemcpyAsync(down + 32, seg_nulls, 4 * nstat_dev, hipMemcpyDeviceToHost, ctx->stream));
+      SQ_HIP(hipMemcpyAsync(down + 32, d.sep_pos->as<uint32_t>() + a_last * C - 1, 4, hipMemcpyDeviceToHost, ctx->stream));
+    SQ_HIP(hipMemcpyAsync(down + 48, seg_nulls, 4 * nstat_dev, hipMemcpyDeviceToHost, ctx->stream));
     ctx->sync();
     c = *(const CsvCtl *)down;
-    d.tail_start_off = a_last > 0 ? d.piece_pos + (int64_t)*(const uint32_t *)(down + 16) + 1 : d.piece_pos;
-    const uint32_t *st = (const uint32_t *)(down + 32);
+    d.tail_start_off = a_last > 0 ? d.piece_pos + (int64_t)*(const uint32_t *)(down + 32) + 1 : d.piece_pos;
+    const uint32_t *st = (const uint32_t *)(down + 48);
     d.seg_nulls.assign(nstat, 0);
     for (size_t i = 0; i < nstat * CSV_NULL_BANKS; i++) d.seg_nulls[i / CSV_NULL_BANKS] += st[i];
     d.seg_bytes.assign(st + nstat * CSV_NULL_BANKS, st + nstat_dev);
@@ -318,8 +356,9 @@ void append_segment(sqlrs_csv *r, CsvDevice &d) {
   }
   {
     ProfScope ps(ctx, "csv_cut");
-    csv_cut_kernel<<<dim3((unsigned)ceil_div(take, CSV_WG), (unsigned)nslots), dim3(CSV_WG), 0, ctx->stream>>>(
-        d.bytes->as<uint8_t>(), d.P, out_params(r, d), a, take, d.fill);
+    const dim3 grid((unsigned)ceil_div(take, CSV_WG), (unsigned)nslots);
+    if (d.piece_quotes) csv_cut_kernel<true><<<grid, dim3(CSV_WG), 0, ctx->stream>>>(d.bytes->as<uint8_t>(), d.P, out_params(r, d), a, take, d.fill);
+    else csv_cut_kernel<false><<<grid, dim3(CSV_WG), 0, ctx->stream>>>(d.bytes->as<uint8_t>(), d.P, out_params(r, d), a, take, d.fill);
     SQ_HIP(hipGetLastError());
   }
   for (int s = 0; s < nslots; s++) {
@@ -440,6 +479,13 @@ int sqlrs_csv_set_device_parse(sqlrs_csv_t *r, int64_t chunk_bytes) {
     if (chunk_bytes == 0) return;
     r->dev = std::make_shared<sq::CsvDevice>();
     r->dev->piece_bytes = chunk_bytes < 0 ? sq::CSV_DEFAULT_PIECE : std::min(chunk_bytes, sq::CSV_MAX_PIECE);
+  });
+}
+
+int sqlrs_csv_set_device_quotes(sqlrs_csv_t *r, int on) {
+  return sq::guard(r->ctx, [&] {
+    if (r->started) sq::fail(SQLRS_ERR_INTERNAL, "sqlrs_csv_set_device_quotes: after the first sqlrs_csv_next_batch");
+    r->device_quotes = on != 0;
   });
 }
 

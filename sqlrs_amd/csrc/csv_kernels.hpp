@@ -1,4 +1,5 @@
-// csv_kernels.hpp — the device form of the CSV reader (csv_device.hip): bytes of one quote-free piece of the file -> columns.
+// csv_kernels.hpp — the device form of the CSV reader (csv_device.hip): bytes of one piece of the file -> columns.  The piece is
+// quote-free, or (sqlrs_csv_set_device_quotes) its quotes are all regular: "quoted fields" below.
 //
 //   classify   16 bytes per lane, 4096 per workgroup: which bytes are separators (a delimiter, or a '\n' that ends a
 //              record — a '\n' that ends a blank line is none), their count per tile, "a '"' was seen"
@@ -22,6 +23,7 @@ constexpr int CSV_LANE_BYTES = 16;
 constexpr int CSV_TILE = CSV_WG * CSV_LANE_BYTES;
 constexpr int CSV_MAX_SLOTS = 32; // projected columns per launch (the parameter block holds their descriptors)
 constexpr uint32_t CSV_NO_ROW = 0xffffffffu;
+constexpr uint32_t CSV_ESCAPES = 0x80000000u; // (a piece is shorter than 2^31 - 64 bytes)
 constexpr int CSV_NULL_BANKS = 8; // counters per (output batch, column) that the NULL counts are spread over
 
 // control words of one piece (device, zeroed / preset before the kernels)
@@ -30,6 +32,11 @@ struct CsvCtl {
   uint32_t first_bad;   // row of the first separator that breaks the f % C rule (CSV_NO_ROW: none)
   uint32_t err_row;     // first row with an unparsable typed field (CSV_NO_ROW: none)
   uint32_t num_patches; // entries on the patch list
+  // ---- sqlrs_csv_set_device_quotes (csv_index_q_kernel)
+  uint32_t bad_quote;     // position of the first irregular quote (CSV_NO_ROW: none)
+  uint32_t last_end_pos;  // position of the last '\n' that ends a record outside quotes (0: none — a '\n' at 0 ends a blank line)
+  uint32_t last_end_rank; // ... and its rank among the separators
+  uint32_t pad_;
 };
 struct CsvPatch {
   uint32_t row, slot, start, len;
@@ -39,8 +46,8 @@ struct CsvSlot {
   int32_t dtype;
   uint64_t *val;   // typed: 8 value bytes per row of the piece (Boolean: 0 / 1)
   uint8_t *flag;   // typed: 1 = valid
-  uint32_t *ustart; // Utf8: first byte of the field in the piece
-  uint32_t *ulen;   // Utf8: its length; [rows] = 0 (scanned into uoff[rows + 1])
+  uint32_t *ustart; // Utf8: first byte of the field in the piece (CSV_ESCAPES set: a quoted field with "" pairs inside)
+  uint32_t *ulen;   // Utf8: its length, a "" pair counted once; [rows] = 0 (scanned into uoff[rows + 1])
   const uint32_t *uoff;
 };
 struct CsvParams {
@@ -135,6 +142,145 @@ __global__ __launch_bounds__(CSV_WG) void csv_index_kernel(const uint8_t *__rest
   if (bad_row != CSV_NO_ROW) atomicMin(&ctl->first_bad, bad_row);
 }
 
+// ---- quoted fields (sqlrs_csv_set_device_quotes) ---------------------------------------------------------------------------------
+// Every '"' toggles "inside quotes"; par(i) = number of quotes in [0, i) mod 2, and a piece starts outside.  That is what the
+// host parser reads exactly when every quote is REGULAR: one with par = 0 (it opens) is the piece's first byte or follows the
+// delimiter, a '\n' or a quote (which closed: an escaped pair); one with par = 1 (it closes) is followed by the delimiter,
+// '\n', "\r\n" or a quote.  The kernels find the separators outside quotes and the first irregular quote; a piece with one in
+// front of its last record end is the host parser's.
+//
+//   quotes     '"' bytes per tile; scanned, the low bit is the tile's starting parity
+//   classify_q / index_q   csv_classify / csv_index with delimiters and record ends inside quotes masked out; index_q also
+//              checks the two regularity rules and keeps the last record end outside quotes: the piece is cut there
+
+// the lane's 16 bytes: bit k = byte i0 + k is a '"'
+__device__ __forceinline__ uint32_t csv_quotes16(const uint8_t *__restrict__ b, int64_t n, int64_t i0) {
+  if (i0 >= n) return 0;
+  const uint4 q = *(const uint4 *)(b + i0);
+  const uint32_t qs[4] = {q.x, q.y, q.z, q.w};
+  uint32_t quotes = 0;
+#pragma unroll
+  for (int k = 0; k < CSV_LANE_BYTES; k++) quotes |= (uint32_t)((uint8_t)(qs[k >> 2] >> (8 * (k & 3))) == '"') << k;
+  return quotes & (n - i0 >= CSV_LANE_BYTES ? 0xffffu : (1u << (int)(n - i0)) - 1);
+}
+
+__global__ __launch_bounds__(CSV_WG) void csv_quotes_kernel(const uint8_t *__restrict__ b, int64_t n, uint32_t *__restrict__ tile_quotes) {
+  __shared__ uint32_t s_wave[CSV_WG / 64];
+  const int64_t i0 = ((int64_t)blockIdx.x * CSV_WG + threadIdx.x) * CSV_LANE_BYTES;
+  const uint32_t cnt = wave_sum_u32((uint32_t)__popc(csv_quotes16(b, n, i0)));
+  if (lane_id() == 0) s_wave[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) tile_quotes[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+}
+
+// csv_masks16 outside quotes.  `delims` / `ends` are the separators with par = 0; `bad` the irregular quotes of the lane.
+// Every lane of the workgroup calls it (a barrier inside); s_par holds one word per wave.
+__device__ __forceinline__ void csv_masks16_q(const uint8_t *__restrict__ b, int64_t n, int64_t i0, uint8_t delim, uint32_t tile_par,
+                                              uint32_t *s_par, uint32_t &delims, uint32_t &ends, uint32_t &bad) {
+  uint32_t quotes = 0, open_ok = 0, close_ok = 0;
+  delims = ends = 0;
+  if (i0 < n) {
+    const uint4 q = *(const uint4 *)(b + i0); // (the buffer is padded to whole 16 bytes, and 16 more)
+    uint8_t w[CSV_LANE_BYTES + 4];
+    w[0] = i0 >= 2 ? b[i0 - 2] : (uint8_t)'\n';
+    w[1] = i0 >= 1 ? b[i0 - 1] : (uint8_t)'\n';
+    w[CSV_LANE_BYTES + 2] = i0 + CSV_LANE_BYTES < n ? b[i0 + CSV_LANE_BYTES] : (uint8_t)0; // (a piece ends in '\n': no quote of it looks further)
+    w[CSV_LANE_BYTES + 3] = i0 + CSV_LANE_BYTES + 1 < n ? b[i0 + CSV_LANE_BYTES + 1] : (uint8_t)0;
+    const uint32_t qs[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int k = 0; k < CSV_LANE_BYTES; k++) w[k + 2] = (uint8_t)(qs[k >> 2] >> (8 * (k & 3)));
+#pragma unroll
+    for (int k = 0; k < CSV_LANE_BYTES; k++) {
+      const uint8_t c = w[k + 2], p = w[k + 1], x = w[k + 3];
+      const bool blank = p == '\n' || (p == '\r' && w[k] == '\n');
+      delims |= (uint32_t)(c == delim) << k;
+      ends |= (uint32_t)(c == '\n' && c != delim && !blank) << k;
+      quotes |= (uint32_t)(c == '"') << k;
+      open_ok |= (uint32_t)(p == delim || p == '\n' || p == '"') << k; // (the byte in front of the piece reads as '\n')
+      close_ok |= (uint32_t)(x == delim || x == '\n' || x == '"' || (x == '\r' && w[k + 4] == '\n')) << k;
+    }
+    const uint32_t live = n - i0 >= CSV_LANE_BYTES ? 0xffffu : (1u << (int)(n - i0)) - 1;
+    delims &= live;
+    ends &= live;
+    quotes &= live;
+  }
+  // parity in front of the lane: the tile's, the earlier waves', the earlier lanes' of this wave
+  const uint64_t odd = __ballot(__popc(quotes) & 1);
+  const int wv = threadIdx.x >> 6;
+  if (lane_id() == 0) s_par[wv] = (uint32_t)__popcll(odd);
+  __syncthreads();
+  uint32_t par = tile_par + (uint32_t)mbcnt(odd);
+  for (int k = 0; k < wv; k++) par += s_par[k];
+  // bit k of inq = par(i0 + k): the prefix XOR of the quote mask, exclusive, on top of the lane's starting parity
+  uint32_t x = quotes;
+  x ^= x << 1;
+  x ^= x << 2;
+  x ^= x << 4;
+  x ^= x << 8;
+  const uint32_t inq = ((x ^ quotes) ^ ((par & 1) ? 0xffffu : 0u)) & 0xffffu;
+  delims &= ~inq & ~quotes; // (a '"' delimiter: the host side does not come here)
+  ends &= ~inq;
+  bad = quotes & ((~inq & ~open_ok) | (inq & ~close_ok));
+}
+
+__global__ __launch_bounds__(CSV_WG) void csv_classify_q_kernel(const uint8_t *__restrict__ b, int64_t n, uint8_t delim,
+                                                                const uint32_t *__restrict__ tile_qoff, uint32_t *__restrict__ tile_cnt) {
+  __shared__ uint32_t s_par[CSV_WG / 64], s_wave[CSV_WG / 64];
+  const int64_t i0 = ((int64_t)blockIdx.x * CSV_WG + threadIdx.x) * CSV_LANE_BYTES;
+  uint32_t delims, ends, bad;
+  csv_masks16_q(b, n, i0, delim, tile_qoff[blockIdx.x], s_par, delims, ends, bad);
+  const uint32_t cnt = wave_sum_u32((uint32_t)__popc(delims | ends));
+  if (lane_id() == 0) s_wave[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+}
+
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, m, 64));
+  return v;
+}
+
+__global__ __launch_bounds__(CSV_WG) void csv_index_q_kernel(const uint8_t *__restrict__ b, int64_t n, uint8_t delim, uint32_t C,
+                                                             const uint32_t *__restrict__ tile_qoff, const uint32_t *__restrict__ tile_off,
+                                                             uint32_t *__restrict__ sep_pos, CsvCtl *__restrict__ ctl) {
+  __shared__ uint32_t s_par[CSV_WG / 64], s_wave[CSV_WG / 64];
+  const int64_t i0 = ((int64_t)blockIdx.x * CSV_WG + threadIdx.x) * CSV_LANE_BYTES;
+  uint32_t delims, ends, bad;
+  csv_masks16_q(b, n, i0, delim, tile_qoff[blockIdx.x], s_par, delims, ends, bad);
+  const uint32_t cnt = (uint32_t)__popc(delims | ends);
+  const uint32_t incl = wave_iscan_u32(cnt);
+  const int w = threadIdx.x >> 6;
+  if (lane_id() == 63) s_wave[w] = incl;
+  __syncthreads();
+  uint32_t rank = tile_off[blockIdx.x] + incl - cnt;
+  for (int k = 0; k < w; k++) rank += s_wave[k];
+  uint32_t seps = delims | ends, bad_row = CSV_NO_ROW, end_pos = 0, end_rank = 0;
+  while (seps) {
+    const int k = __ffs(seps) - 1;
+    seps &= seps - 1;
+    sep_pos[rank] = (uint32_t)(i0 + k);
+    const bool last_col = rank % C == C - 1, is_end = (ends >> k) & 1;
+    if (last_col != is_end) bad_row = min(bad_row, rank / C);
+    if (is_end) {
+      end_pos = (uint32_t)(i0 + k);
+      end_rank = rank;
+    }
+    rank++;
+  }
+  if (bad_row != CSV_NO_ROW) atomicMin(&ctl->first_bad, bad_row);
+  // one atomic per wave: positions and ranks grow together, so the two maxima belong to the same separator
+  const uint32_t wave_bad = wave_min_u32(bad ? (uint32_t)(i0 + __ffs(bad) - 1) : CSV_NO_ROW);
+  const uint32_t wave_end = wave_max_u32(end_pos), wave_rank = wave_max_u32(end_rank);
+  if (lane_id() == 0) {
+    if (wave_bad != CSV_NO_ROW) atomicMin(&ctl->bad_quote, wave_bad);
+    if (wave_end) {
+      atomicMax(&ctl->last_end_pos, wave_end);
+      atomicMax(&ctl->last_end_rank, wave_rank);
+    }
+  }
+}
+
 __device__ const double csv_pow10[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
                                          1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
 
@@ -220,6 +366,11 @@ __device__ __forceinline__ uint32_t csv_segment(int64_t row, int64_t seg_first, 
 
 // grid: (rows + 1 over CSV_WG, slots).  seg_nulls[(segment * nslots + slot) * CSV_NULL_BANKS + bank], summed over the banks by the
 // host, counts the NULLs a batch gets from this piece.
+// Q (sqlrs_csv_set_device_quotes): a field that starts with '"' also ends in one — every quote of the rows is regular — and its
+// value is what lies between them with "" read as '"'.  The host parser pops one '\r' from the end of a record's text at '\n'
+// even when it came from inside the quotes: a closing quote directly in front of the record's '\n' drops a '\r' before it.
+// A typed field with a quote left inside is an error (the host parser's to raise), as is a field the rule does not explain.
+template <bool Q>
 __global__ __launch_bounds__(CSV_WG) void csv_parse_kernel(const uint8_t *__restrict__ b, const uint32_t *__restrict__ sep_pos,
                                                            const CsvParams P, uint32_t *__restrict__ seg_nulls,
                                                            CsvPatch *__restrict__ patches, CsvCtl *__restrict__ ctl) {
@@ -240,14 +391,29 @@ __global__ __launch_bounds__(CSV_WG) void csv_parse_kernel(const uint8_t *__rest
         else break;
       }
     if (S.src == P.C - 1 && end > start && b[end - 1] == '\r') end--; // one trailing '\r' of the record
+    uint32_t inner_quotes = 0;
+    bool quote_error = false;
+    if (Q && end > start && b[start] == '"') {
+      if (end - start < 2 || b[end - 1] != '"') quote_error = true;
+      else {
+        const bool at_newline = b[end] == '\n';
+        start++;
+        end--;
+        if (at_newline && end > start && b[end - 1] == '\r') end--;
+        for (uint32_t k = start; k < end; k++) inner_quotes += b[k] == '"';
+        quote_error = (inner_quotes & 1) != 0;
+      }
+    }
     if (utf8) {
-      S.ustart[row] = start;
-      S.ulen[row] = end - start;
+      if (quote_error) atomicMin(&ctl->err_row, (uint32_t)row);
+      S.ustart[row] = start | (inner_quotes ? CSV_ESCAPES : 0u);
+      S.ulen[row] = quote_error ? 0u : end - start - inner_quotes / 2;
     } else {
       uint64_t v = 0;
       int res = CSV_FIELD_OK;
       null_row = start == end;
-      if (!null_row) {
+      if (quote_error || inner_quotes) res = CSV_FIELD_ERROR;
+      else if (!null_row) {
         if (S.dtype == SQLRS_INT64) res = csv_parse_int64(b + start, b + end, v);
         else if (S.dtype == SQLRS_FLOAT64) res = csv_parse_float64(b + start, b + end, v);
         else res = csv_parse_bool(b + start, b + end, v);
@@ -291,6 +457,8 @@ __global__ void csv_patch_kernel(const CsvParams P, const CsvPatch *__restrict__
 }
 
 // rows [a, a + cnt) of the piece -> rows [fill, fill + cnt) of the batch under construction; grid: (cnt over CSV_WG, slots)
+// Q: a Utf8 field marked CSV_ESCAPES is copied without the second quote of each "" pair
+template <bool Q>
 __global__ __launch_bounds__(CSV_WG) void csv_cut_kernel(const uint8_t *__restrict__ b, const CsvParams P, const CsvOutParams O,
                                                          int64_t a, int64_t cnt, int64_t fill) {
   const int64_t i = (int64_t)blockIdx.x * CSV_WG + threadIdx.x;
@@ -302,8 +470,18 @@ __global__ __launch_bounds__(CSV_WG) void csv_cut_kernel(const uint8_t *__restri
     const uint32_t dst = D.ubase + (o - o0);
     if (i == 0) D.offsets[fill] = (int32_t)D.ubase;
     D.offsets[fill + i + 1] = (int32_t)(dst + len);
-    const uint8_t *src = b + S.ustart[a + i];
-    for (uint32_t k = 0; k < len; k++) D.bytes[dst + k] = src[k];
+    const uint32_t st = S.ustart[a + i];
+    if (Q && (st & CSV_ESCAPES)) {
+      const uint8_t *src = b + (st & ~CSV_ESCAPES);
+      for (uint32_t k = 0; k < len; k++) {
+        const uint8_t c = *src;
+        D.bytes[dst + k] = c;
+        src += c == '"' ? 2 : 1;
+      }
+    } else {
+      const uint8_t *src = b + st;
+      for (uint32_t k = 0; k < len; k++) D.bytes[dst + k] = src[k];
+    }
   } else {
     const uint64_t v = S.val[a + i];
     const uint8_t ok = S.flag[a + i];

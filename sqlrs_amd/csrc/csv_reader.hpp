@@ -20,7 +20,9 @@ struct sqlrs_csv {
   uint64_t remaining = ~0ull;  // records still allowed by the bounds
   uint64_t line = 0;           // for error messages
   bool has_header = true;
+  bool started = false;        // sqlrs_csv_next_batch has been called
   std::shared_ptr<sq::CsvDevice> dev; // sqlrs_csv_set_device_parse: the device parser's state (null: host parser)
+  bool device_quotes = false;  // sqlrs_csv_set_device_quotes: the device parser also takes pieces whose quotes are all regular
 };
 
 namespace sq {

@@ -862,6 +862,7 @@ int sqlrs_csv_set_projection(sqlrs_csv_t *r, int num_columns, const int32_t *col
 // next batch of <= batch_size records, *out = NULL at the end of the scan [ref: csv.rs:236-241]
 int sqlrs_csv_next_batch(sqlrs_csv_t *r, int out_mem, sqlrs_batch_t **out) {
   return guard(r->ctx, [&] {
+    r->started = true;
     if (r->dev) csv_device_next_batch(r, out_mem, out);
     else csv_host_next_batch(r, out_mem, out);
   });

@@ -533,14 +533,16 @@ class CsvScan:
     batches of ``batch_size`` rows; ``bounds = (offset, limit)``, ``projection`` = column indices.
     HIP library only (CSV ingest is host work that lands in HBM with ``out_mem=MEM_DEVICE``).
     ``device_parse``: ``None`` = the host parser; an int = the argument of ``sqlrs_csv_set_device_parse`` (a piece
-    size in bytes, or < 0 for the library's) — the same batches, parsed by the device kernels.  ``stats`` holds
+    size in bytes, or < 0 for the library's) — the same batches, parsed by the device kernels.  ``device_quotes``:
+    ``None`` = no call; otherwise the argument of ``sqlrs_csv_set_device_quotes`` (1: pieces whose quotes are all regular
+    are parsed on the device too).  ``stats`` holds
     ``device_rows`` / ``host_rows`` / ``patched_fields`` once ``execute()`` has run (also after an error)."""
 
     def __init__(self, backend: abi.Backend, path: str, has_header: bool = True, delimiter: str = ",",
                  batch_size: int = 1024, infer_max_records: int = 10, bounds=None, projection=None,
-                 out_mem: int = abi.MEM_HOST, device_parse=None):
+                 out_mem: int = abi.MEM_HOST, device_parse=None, device_quotes=None):
         self.backend, self.path, self.out_mem = backend, path, out_mem
-        self.device_parse = device_parse
+        self.device_parse, self.device_quotes = device_parse, device_quotes
         self.stats = None
         self.cfg = (has_header, delimiter, batch_size, infer_max_records)
         self.bounds, self.projection = bounds, projection
@@ -566,6 +568,8 @@ class CsvScan:
                 be.check(be.fn("csv_set_bounds")(h, int(self.bounds[0]), -1 if self.bounds[1] is None else int(self.bounds[1])))
             if self.device_parse is not None:
                 be.check(be.fn("csv_set_device_parse")(h, int(self.device_parse)))
+            if self.device_quotes is not None:
+                be.check(be.fn("csv_set_device_quotes")(h, int(self.device_quotes)))
             while True:
                 out = C.POINTER(abi.Batch)()
                 be.check(be.fn("csv_next_batch")(h, self.out_mem, C.byref(out)))
@@ -573,7 +577,7 @@ class CsvScan:
                     break
                 yield _emit(be, out, self.out_mem, names)
         finally:
-            if self.device_parse is not None:
+            if self.device_parse is not None or self.device_quotes is not None:
                 d, hr, pf = C.c_int64(), C.c_int64(), C.c_int64()
                 be.fn("csv_device_stats")(h, C.byref(d), C.byref(hr), C.byref(pf))
                 self.stats = {"device_rows": d.value, "host_rows": hr.value, "patched_fields": pf.value}
