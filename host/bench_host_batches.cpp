@@ -4,6 +4,7 @@
 // ctypes call per batch.  Prints one JSON object; `bench.py` adds it to the line as `C4_host_batches_1024_native`.
 //   ./bench_host_batches [rows = 2e7] [groups = 1e6] [batch = 1024]
 //   ./bench_host_batches filter ... | probe ...   the streaming operators at the same batch shape (see bench_filter / bench_probe)
+//   ./bench_host_batches probe_general ...         outer joins / duplicate build keys through push_async (see bench_probe_general)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -435,7 +436,132 @@ static int bench_project(int argc, char **argv) {
   return ok ? 0 : 1;
 }
 
+// ./bench_host_batches probe_general [rows = 2e7] [build = 1e6] [batch = 1024] [join = left|right|full|inner] [dup = 1|4]
+// The probe stream of bench_probe against a build side whose every key is carried by `dup` rows (build / dup distinct keys;
+// a fifth of the probe keys has no partner), joined as `join`, through three paths: sqlrs_hash_join_probe_push per batch,
+// sqlrs_hash_join_probe_push_async with sqlrs_hash_join_set_async_general off (the synchronous operator inside push_async) and
+// on (one launch per batch), DEPTH tickets in flight.  The off and on runs alternate; best of 2 after a warm-up each; the
+// joined rows (tail batch of Left / Full included) of the three paths must agree.
+static int bench_probe_general(int argc, char **argv) {
+  const int64_t n = argc > 2 ? (int64_t)std::atof(argv[2]) : 20000000, nB = argc > 3 ? (int64_t)std::atof(argv[3]) : 1000000;
+  const int64_t B = argc > 4 ? std::atoll(argv[4]) : 1024;
+  const char *jname = argc > 5 ? argv[5] : "left";
+  const int64_t dup = argc > 6 ? std::max<int64_t>(1, std::atoll(argv[6])) : 1;
+  const int jt = std::strcmp(jname, "inner") == 0 ? SQLRS_JOIN_INNER : std::strcmp(jname, "right") == 0 ? SQLRS_JOIN_RIGHT
+                 : std::strcmp(jname, "full") == 0 ? SQLRS_JOIN_FULL : SQLRS_JOIN_LEFT;
+  sqlrs_ctx_t *ctx = nullptr;
+  if (sqlrs_ctx_create(0, &ctx) != SQLRS_OK) {
+    std::printf("{\"error\": \"no device\"}\n");
+    return 2;
+  }
+  const int64_t nkeys = std::max<int64_t>(1, nB / dup);
+  std::vector<int64_t> dk((size_t)nB), dp((size_t)nB), fk((size_t)n);
+  std::vector<double> fv((size_t)n);
+  for (int64_t i = 0; i < nB; i++) {
+    dk[(size_t)i] = ((i * 7919) % nB) % nkeys;
+    dp[(size_t)i] = dk[(size_t)i] * 3 + 1;
+  }
+  for (int64_t i = 0; i < n; i++) {
+    fk[(size_t)i] = (int64_t)(splitmix64(0xF1, (uint64_t)i) % (uint64_t)(nkeys + nkeys / 4));
+    fv[(size_t)i] = (double)(splitmix64(0xF2, (uint64_t)i) >> 11) * (1.0 / 9007199254740992.0);
+  }
+  sqlrs_expr_node_t k0{};
+  k0.op = SQLRS_EXPR_INPUT_REF;
+  k0.index = 0;
+  sqlrs_expr_t key{&k0, 1, 0};
+  const int32_t right_dtypes[2] = {SQLRS_INT64, SQLRS_FLOAT64};
+  const int DEPTH = 8;
+  const int64_t nb = (n + B - 1) / B;
+  double best[3] = {1e30, 1e30, 1e30}; // push, push_async switch off, push_async switch on
+  int64_t joined[3] = {0, 0, 0};
+  bool ok = true;
+  auto run = [&](int path, int rep) -> int { // 0 ok
+    auto t0 = std::chrono::steady_clock::now();
+    sqlrs_hash_join_t *j = nullptr;
+    CHECK(sqlrs_hash_join_create(ctx, jt, 1, &key, &key, nullptr, 2, right_dtypes, &j));
+    if (path == 2) CHECK(sqlrs_hash_join_set_async_general(j, 1));
+    sqlrs_column_t lc[2];
+    host_col(lc[0], SQLRS_INT64, dk.data(), nB);
+    host_col(lc[1], SQLRS_INT64, dp.data(), nB);
+    sqlrs_batch_t lb{};
+    lb.num_rows = nB;
+    lb.num_columns = 2;
+    lb.columns = lc;
+    CHECK(sqlrs_hash_join_build_push(j, &lb));
+    CHECK(sqlrs_hash_join_build_finish(j));
+    int64_t got = 0;
+    auto consume = [&](sqlrs_batch_t *o) { // a matched row carries payload 3 * key + 1 beside the probe row's key
+      if (!o) return;
+      if (rep == 0 && o->num_rows) {
+        const int64_t *p = (const int64_t *)o->columns[1].values, *rk = (const int64_t *)o->columns[2].values;
+        const uint8_t *pv = (const uint8_t *)o->columns[1].validity;
+        for (int64_t r = 0; r < o->num_rows; r += 97) {
+          const bool matched = rk[r] < nkeys;
+          const bool valid = !pv || !o->columns[1].null_count || ((pv[r >> 3] >> (r & 7)) & 1);
+          ok = ok && matched == valid && (!matched || p[r] == 3 * rk[r] + 1);
+        }
+      }
+      got += o->num_rows;
+      sqlrs_batch_release(o);
+    };
+    std::vector<sqlrs_ticket_t *> q((size_t)DEPTH, nullptr);
+    for (int64_t b = 0; b < nb + (path ? DEPTH : 0); b++) {
+      if (path && b >= DEPTH) {
+        sqlrs_batch_t *o = nullptr;
+        CHECK(sqlrs_batch_wait(q[(size_t)(b % DEPTH)], &o));
+        consume(o);
+      }
+      if (b >= nb) continue;
+      const int64_t lo = b * B, m = std::min<int64_t>(B, n - lo);
+      sqlrs_column_t rc[2];
+      host_col(rc[0], SQLRS_INT64, fk.data() + lo, m);
+      host_col(rc[1], SQLRS_FLOAT64, fv.data() + lo, m);
+      sqlrs_batch_t rb{};
+      rb.num_rows = m;
+      rb.num_columns = 2;
+      rb.columns = rc;
+      if (path) {
+        CHECK(sqlrs_hash_join_probe_push_async(j, &rb, &q[(size_t)(b % DEPTH)]));
+      } else {
+        sqlrs_batch_t *o = nullptr;
+        CHECK(sqlrs_hash_join_probe_push(j, &rb, SQLRS_MEM_HOST, &o));
+        consume(o);
+      }
+    }
+    sqlrs_batch_t *tail = nullptr;
+    CHECK(sqlrs_hash_join_finish(j, SQLRS_MEM_HOST, &tail));
+    if (tail) {
+      got += tail->num_rows;
+      sqlrs_batch_release(tail);
+    }
+    sqlrs_hash_join_destroy(j);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    joined[path] = got;
+    if (rep > 0 && ms < best[path]) best[path] = ms;
+    return 0;
+  };
+  for (int rep = 0; rep < 3; rep++)
+    if (run(0, rep)) return 1;
+  for (int rep = 0; rep < 3; rep++) // off and on alternate
+    for (int path = 1; path <= 2; path++)
+      if (run(path, rep)) return 1;
+  ok = ok && joined[0] == joined[1] && joined[1] == joined[2] && joined[0] > 0;
+  std::printf("{\"mode\": \"probe_general\", \"join\": \"%s\", \"dup\": %lld, \"probe_rows\": %lld, \"build_rows\": %lld, \"batch_rows\": %lld, "
+              "\"joined\": %lld, \"depth\": %d, \"ms_push\": %.1f, \"Mrows_s_push\": %.1f, \"ms_push_async_off\": %.1f, \"Mrows_s_push_async_off\": %.1f, "
+              "\"ms_push_async_on\": %.1f, \"Mrows_s_push_async_on\": %.1f, \"on_over_off\": %.2f, \"check\": \"%s\", \"note\": \"native caller "
+              "(C ABI): build side one host batch (every key %lld times), probe side pageable %lld-row host batches (a fifth of the keys "
+              "without partner), joined batches on the host; push = sqlrs_hash_join_probe_push per batch, push_async_off / _on = "
+              "sqlrs_hash_join_probe_push_async with sqlrs_hash_join_set_async_general 0 / 1 (alternating runs); Mrows/s = probe rows; "
+              "build included; best of 2 after a warm-up\"}\n",
+              jname, (long long)dup, (long long)n, (long long)nB, (long long)B, (long long)joined[0], DEPTH, best[0], (double)n / best[0] / 1e3,
+              best[1], (double)n / best[1] / 1e3, best[2], (double)n / best[2] / 1e3, best[1] / best[2], ok ? "OK" : "mismatch", (long long)dup,
+              (long long)B);
+  sqlrs_ctx_destroy(ctx);
+  return ok ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
+  if (argc > 1 && std::strcmp(argv[1], "probe_general") == 0) return bench_probe_general(argc, argv);
   if (argc > 1 && std::strcmp(argv[1], "filter") == 0) return bench_filter(argc, argv);
   if (argc > 1 && std::strcmp(argv[1], "project") == 0) return bench_project(argc, argv);
   if (argc > 1 && std::strcmp(argv[1], "probe") == 0) return bench_probe(argc, argv);

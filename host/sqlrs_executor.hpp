@@ -465,6 +465,7 @@ struct HashJoinExecutor { // hash_join.rs:16-23
   size_t num_left_columns; // where the right part of join_output_schema starts
   size_t group = 0;        // probe batches per library call (see FilterExecutor)
   size_t depth = 0;        // probe batches through sqlrs_hash_join_probe_push_async, that many tickets in flight (see FilterExecutor)
+  bool async_general = false; // sqlrs_hash_join_set_async_general: with depth > 0, outer joins and duplicate build keys in one launch per batch too
 
   BoxedExecutor execute() {
     struct S : Executor {
@@ -553,6 +554,7 @@ struct HashJoinExecutor { // hash_join.rs:16-23
     if (join_condition.on.empty()) throw ExecutorError(ExecutorError::InternalError, "HashJoin must has on condition");
     ctx->check(sqlrs_hash_join_create(ctx->raw, (int)join_type, (int)lke.size(), lke.data(), rke.data(),
                                       join_condition.filter ? &fe : nullptr, (int)right_dtypes.size(), right_dtypes.data(), &s->j));
+    if (async_general) ctx->check(sqlrs_hash_join_set_async_general(s->j, 1));
     return s;
   }
 };

@@ -331,6 +331,31 @@ int sqlrs_hash_join_probe_push_many(sqlrs_hash_join_t *j, int n, const sqlrs_bat
  * float64, no NULL probe keys), unique build keys and fixed-width columns on both sides; *out of the wait is NULL for an
  * empty build side, as for probe_push. */
 int sqlrs_hash_join_probe_push_async(sqlrs_hash_join_t *j, const sqlrs_batch_t *right, sqlrs_ticket_t **ticket);
+/* on != 0: sqlrs_hash_join_probe_push_async also serves, in one launch per batch, Left / Right / Full joins and build
+ * sides with duplicate keys (below).  Default 0: exactly today's behaviour.  Call after sqlrs_hash_join_create and before
+ * the first probe call of any kind (later: SQLRS_ERR_INTERNAL).  The contract of probe_push_async is unchanged: the
+ * ticket stands for the HOST batch sqlrs_hash_join_probe_push(j, right, SQLRS_MEM_HOST, ..) would have returned.
+ *
+ * Eligibility of a probe batch with the switch on.  Everything the fast path above requires except "Inner" and "unique
+ * build keys": no join filter; ONE exactly compared INPUT_REF key of int32 / int64 / float64 (no composite key, no
+ * match-by-hash); no NULL probe key in the batch; HOST input of at most 4096 rows; int32 / int64 / float64 columns on
+ * both sides, at most 12 output columns; a free ring slot.  In place of the two dropped conditions, the OUTPUT BOUND: let
+ * M be the largest number of build rows that share one key (1 for unique build keys; build rows with a NULL key count as
+ * sharing one key) — a batch of `rows` rows emits at most rows x M joined rows (a Right / Full probe row without a
+ * partner emits one) — and the batch is eligible iff
+ *   rows x M <= 16384 (SA_MAX_OUT_ROWS), and
+ *   64 + sum over the output columns of (round64(width x rows x M) + round64(ceil(rows x M / 8))) <= 524288 (SA_AREA):
+ *   the 64-byte header, every output column (width 4 or 8) and its validity bitmap laid out for rows x M rows, each
+ *   piece rounded up to 64 bytes — and the staged input, round64(width x rows) per probe column plus
+ *   round64(ceil(rows / 8) + 8) per probe column with NULLs, fits 524288 bytes as well (it always does at <= 4096 rows
+ *   and <= 12 columns).
+ * M is computed once per join (one small kernel, one fetch) when it is first needed.  The decision is made on the host
+ * before a slot is taken; there is no overflow and no re-run.  An Inner join over unique build keys keeps the kernel of
+ * the fast path above.  Every other batch — NULL probe keys, join filters, Utf8 / Boolean columns on either side,
+ * composite keys, match-by-hash, DEVICE input, more than 4096 rows, the bound exceeded — runs the synchronous operator
+ * inside push_async, as with the switch off.  Left / Full: sqlrs_hash_join_finish may be called with tickets still
+ * outstanding; it waits for the queued probe kernels (which mark the visited build rows) before it reads the marks. */
+int sqlrs_hash_join_set_async_general(sqlrs_hash_join_t *j, int on);
 /* The index-pair form of one probe batch, before any gather: 2 columns
  * (UINT64 left index, nullable; UINT32 right index), in the reference's order
  * (probe-row major, build insertion order minor), join filter NOT applied.

@@ -63,11 +63,15 @@ int sa_take_slot(SaRing *r) {
 
 static uint32_t sa_width(int32_t dtype) { return dtype == SQLRS_INT32 ? 4u : (dtype == SQLRS_INT64 || dtype == SQLRS_FLOAT64) ? 8u : 0u; }
 
-bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int first_out_col, const int32_t *front_dtypes, bool allow_utf8) {
+bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int first_out_col, const int32_t *front_dtypes, bool allow_utf8,
+                    uint32_t out_rows) {
   if (!in || in->num_rows < 0 || in->num_rows > (int64_t)SA_MAX_ROWS || in->num_columns <= 0 ||
       in->num_columns + first_out_col > SA_MAX_COLS)
     return false;
   const uint32_t rows = (uint32_t)in->num_rows, vbytes = (rows + 7) / 8;
+  if (out_rows == SA_NONE) out_rows = rows;
+  if (out_rows > SA_MAX_OUT_ROWS || (allow_utf8 && out_rows != rows)) return false;
+  const uint32_t out_vbytes = (out_rows + 7) / 8;
   for (int c = 0; c < in->num_columns; c++) {
     const sqlrs_column_t &col = in->columns[c];
     if (col.mem != SQLRS_MEM_HOST || col.length != in->num_rows) return false;
@@ -77,7 +81,7 @@ bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int f
       return false;
   }
   auto up64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
-  // output: header | per column values (`rows` bound both sides) + validity (+ the bytes of a Utf8 column)
+  // output: header | per column values (`out_rows` bound them; = `rows` unless the caller says otherwise) + validity (+ the bytes of a Utf8 column)
   size_t in_at = 0, out_at = up64(sizeof(SaHeader));
   lay->ncols = first_out_col + in->num_columns;
   lay->rows = rows;
@@ -89,11 +93,11 @@ bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int f
     if (!d.width) return false;
     d.in_off = d.in_voff = d.in_data = d.out_data = SA_NONE;
     d.data_base = 0;
-    const size_t nval = utf8 ? (size_t)rows + 1 : rows;
+    const size_t nval = utf8 ? (size_t)rows + 1 : rows, nout = utf8 ? nval : out_rows;
     d.out_off = (uint32_t)out_at;
-    out_at = up64(out_at + (size_t)d.width * nval);
+    out_at = up64(out_at + (size_t)d.width * nout);
     d.out_voff = (uint32_t)out_at;
-    out_at = up64(out_at + vbytes);
+    out_at = up64(out_at + out_vbytes);
     if (c >= first_out_col) {
       const sqlrs_column_t &col = in->columns[c - first_out_col];
       d.in_off = (uint32_t)in_at;
@@ -237,6 +241,7 @@ int sqlrs_batch_wait(sqlrs_ticket_t *ticket, sqlrs_batch_t **out) {
       for (int i = 0; i < SA_STREAMS; i++) SQ_HIP(hipStreamSynchronize(r->side[i]));
       if (__atomic_load_n(&h->seq, __ATOMIC_ACQUIRE) != ticket->seq) fail(SQLRS_ERR_DEVICE, "batch_wait: the batch's kernel left no result");
     }
+    if (h->pad == 2) fail(SQLRS_ERR_INTERNAL, "batch_wait: the probe kernel met more joined rows than its slot was laid out for");
     if (h->pad) fail(SQLRS_ERR_ARROW, "Divide by zero error"); // (what the synchronous evaluator raises at the push, expr.hip)
     const SaLayout &lay = ticket->lay;
     const uint8_t *oa = r->out_area(ticket->slot);

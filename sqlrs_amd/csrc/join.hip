@@ -1175,6 +1175,7 @@ int sqlrs_hash_join_probe_push(sqlrs_hash_join_t *j, const sqlrs_batch_t *right,
   return guard(j->ctx, [&] {
     SQ_HIP(hipSetDevice(j->ctx->device));
     if (!j->finished) fail(SQLRS_ERR_INTERNAL, "probe before build_finish");
+    j->probe_started = true;
     *out = nullptr;
     if (j->empty_build) return;
     InBatch ib(j->ctx, right);
@@ -1307,6 +1308,241 @@ static bool sa_probe_try(sqlrs_hash_join *j, const sqlrs_batch_t *right, sqlrs_t
   t->lay = p.lay;
   return true;
 }
+
+// ---- the same for Left / Right / Full joins and build sides with duplicate keys (sqlrs_hash_join_set_async_general) -------------
+// A probe row emits as many joined rows as its key has build rows (Right / Full: one when it has none, hash_join.rs:241-246), so
+// the batch is not compacted but EXPANDED: every probe row is looked up once ({run start, rows}: the direct-address table, the
+// 16-byte-slot table, or dd_table), the emit counts are scanned over the batch in row order (wave scans + one LDS step per 1024
+// rows), and then one thread per OUTPUT row finds its probe row by binary search in the scanned offsets (LDS) — stores stay
+// coalesced and a hot key does not serialise one thread.  Output row o of probe row r is build row rows_by_slot[start_r + o -
+// off_r]: probe-row major, build insertion order minor, the reference's pair order (hash_join.rs:225-234) and that of
+// join_fill_expand_kernel.  A wave's 64 consecutive output rows are one aligned 8-byte word of a column's validity bitmap: the
+// bitmaps are the waves' ballots (no per-row flags in LDS, no pack pass).  Left / Full: the matched build rows are marked in
+// `visited` (mark_bits_kernel's form) — sqlrs_hash_join_finish drains the side streams before it reads them.
+// Static LDS: 2 x 16 KiB (offsets, run starts) + 116 bytes.  The host admits a batch only when rows x M fits `cap`.
+struct SaProbeGenParams {
+  SaLayout lay;
+  int nleft, key_col, key_is32;
+  int mode; // 0: direct-address table (unique keys), 1: 16-byte-slot table, 2: dd_table (duplicate keys over a dense range)
+  int unique, outer_right, mark;
+  uint32_t cap; // output rows the slot is laid out for
+  const void *lvals[SA_MAX_COLS];
+  const uint64_t *lvalid[SA_MAX_COLS];
+  const Slot *table;
+  uint64_t mask;
+  DenseTable dt;
+  const uint32_t *dd;
+  uint64_t dup_min, dup_range;
+  const uint32_t *rows_by_slot;
+  unsigned long long *visited;
+  const uint8_t *in;
+  uint8_t *out;
+  unsigned long long seq;
+};
+__global__ __launch_bounds__(1024) void sa_probe_general_kernel(SaGroup<SaProbeGenParams> grp) {
+  const SaProbeGenParams &p = grp.p[blockIdx.x]; // (one workgroup per batch of the group)
+  __shared__ uint32_t s_off[SA_MAX_ROWS], s_start[SA_MAX_ROWS]; // per probe row: first output row; run start / build row / DENSE_EMPTY
+  __shared__ uint32_t s_w[16], s_nulls[SA_MAX_COLS], s_err;
+  const int lane = lane_id(), w = wave_id();
+  if (threadIdx.x < SA_MAX_COLS) s_nulls[threadIdx.x] = 0;
+  if (threadIdx.x == 0) s_err = 0;
+  const uint32_t rows = p.lay.rows;
+  const SaCol &kc = p.lay.c[p.nleft + p.key_col];
+  uint32_t base = 0;
+  for (uint32_t t = 0; t * 1024u < rows; t++) { // (uniform)
+    const uint32_t r = t * 1024u + threadIdx.x;
+    uint32_t e = 0, start = DENSE_EMPTY;
+    if (r < rows) {
+      const uint64_t key = p.key_is32 ? (uint64_t)(int64_t)((const int32_t *)(p.in + kc.in_off))[r] : ((const uint64_t *)(p.in + kc.in_off))[r];
+      uint32_t cnt = 0;
+      if (p.mode == 0) {
+        const uint64_t d = key - p.dt.kmin;
+        start = dense_get(p.dt, d < p.dt.range ? d : p.dt.range + 1);
+        cnt = start != DENSE_EMPTY;
+      } else if (p.mode == 1) {
+        const Slot sl = probe_slot(p.table, p.mask, key, false);
+        start = sl.head;
+        cnt = sl.count;
+      } else {
+        const uint64_t d = key - p.dup_min;
+        const uint32_t *en = p.dd + (d < p.dup_range ? d : p.dup_range + 1); // (a key outside the range reads the empty run behind it)
+        start = en[0];
+        cnt = en[1] - start;
+      }
+      if (!cnt) start = DENSE_EMPTY;
+      e = cnt ? cnt : (uint32_t)p.outer_right;
+    }
+    const uint32_t inc = wave_iscan_u32(e);
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (int q = 0; q < 16; q++) {
+      const uint32_t c = s_w[q];
+      before += q < w ? c : 0;
+      all += c;
+    }
+    if (r < rows) {
+      s_off[r] = base + before + inc - e;
+      s_start[r] = start;
+    }
+    base += all;
+    __syncthreads();
+  }
+  uint32_t total = base;
+  if (total > p.cap) { // (cannot happen while the host's M is right: nothing is written past the slot, the wait reports it)
+    total = 0;
+    if (threadIdx.x == 0) s_err = 2;
+  }
+  for (uint32_t o0 = 0; o0 < total; o0 += 1024u) { // (uniform)
+    const uint32_t o = o0 + threadIdx.x;
+    const bool act = o < total;
+    uint32_t r = 0, brow = DENSE_EMPTY;
+    if (act) {
+      uint32_t lo = 0, hi = rows; // the last probe row whose first output row is <= o (s_off[0] = 0)
+      while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (s_off[mid] <= o) lo = mid;
+        else hi = mid;
+      }
+      r = lo;
+      const uint32_t st = s_start[r];
+      if (st != DENSE_EMPTY) brow = p.unique ? st : p.rows_by_slot[st + (o - s_off[r])];
+      if (p.mark && brow != DENSE_EMPTY) { // (bits only ever get set: a plain read decides whether the atomic is needed, mark_bits_kernel)
+        const unsigned long long bit = 1ull << (brow & 63);
+        if (!(__hip_atomic_load(&p.visited[brow >> 6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) atomicOr(&p.visited[brow >> 6], bit);
+      }
+    }
+    const uint64_t actm = __ballot(act);
+    for (int c = 0; c < p.lay.ncols; c++) {
+      const SaCol &col = p.lay.c[c];
+      const bool left = c < p.nleft;
+      const uint8_t *rvalid = !left && col.in_voff != SA_NONE ? p.in + col.in_voff : nullptr;
+      const uint64_t *lvalid = left ? p.lvalid[c] : nullptr;
+      const uint8_t *src = left ? (const uint8_t *)p.lvals[c] : p.in + col.in_off;
+      bool valid = true;
+      if (act) {
+        const uint32_t s = left ? brow : r;
+        valid = s != DENSE_EMPTY; // (a probe row without partner: NULL in every build column)
+        if (col.width == 8) ((uint64_t *)(p.out + col.out_off))[o] = valid ? ((const uint64_t *)src)[s] : 0ull;
+        else ((uint32_t *)(p.out + col.out_off))[o] = valid ? ((const uint32_t *)src)[s] : 0u;
+        if (valid && lvalid) valid = (lvalid[s >> 6] >> (s & 63)) & 1;
+        else if (rvalid) valid = (rvalid[s >> 3] >> (s & 7)) & 1;
+      }
+      if (lvalid || rvalid || (left && p.outer_right)) { // (uniform) the column may hold NULLs: 64 output rows = one word of its bitmap
+        const uint64_t bm = __ballot(act && valid);
+        if (lane == 0 && actm) {
+          *(uint64_t *)(p.out + col.out_voff + ((o0 + 64u * (uint32_t)w) >> 3)) = bm;
+          const uint32_t nulls = (uint32_t)__popcll(actm & ~bm);
+          if (nulls) atomicAdd(&s_nulls[c], nulls);
+        }
+      }
+    }
+  }
+  sa_publish((SaHeader *)p.out, p.seq, total, s_nulls, p.lay.ncols, &s_err);
+}
+static void sa_probe_general_launch(SaRing *r, Ctx *ctx) {
+  SaGroup<SaProbeGenParams> g;
+  for (int i = 0; i < r->pend_n; i++) std::memcpy(&g.p[i], r->pend_buf + (size_t)i * SA_PARAM_MAX, sizeof(SaProbeGenParams));
+  sa_probe_general_kernel<<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g);
+  SQ_HIP(hipGetLastError());
+}
+// M: the most build rows that share one key — the largest Slot.count of the 16-byte-slot table (its NULL-key slot included) or
+// the longest run of dd_table
+__global__ void sa_max_run_kernel(const Slot *__restrict__ table, const uint32_t *__restrict__ dd, int64_t n, uint32_t *__restrict__ out) {
+  uint32_t m = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    m = max(m, table ? table[i].count : dd[i + 1] - dd[i]);
+  for (int s = 32; s >= 1; s >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, s, 64));
+  if (lane_id() == 0 && m) atomicMax(out, m);
+}
+// once per join, on first need: unique build keys need no kernel
+static uint32_t hash_join_max_run(sqlrs_hash_join *j) {
+  if (j->unique) return 1;
+  if (!j->max_run) {
+    Ctx *ctx = j->ctx;
+    const int64_t n = j->dd_table ? (int64_t)j->dup_range : (int64_t)j->mask + 3; // (dd_table[range] = rows ends the last run; cap + 2 slots)
+    BufP out = ctx->alloc_zero(8);
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 256 * 4), 4 * (int64_t)ctx->num_cus));
+    sa_max_run_kernel<<<dim3(blocks), dim3(256), 0, ctx->stream>>>(j->dd_table ? nullptr : j->table->as<Slot>(),
+                                                                  j->dd_table ? j->dd_table->as<uint32_t>() : nullptr, n, out->as<uint32_t>());
+    SQ_HIP(hipGetLastError());
+    j->max_run = std::max(1u, ctx->fetch_value(out->as<uint32_t>()));
+  }
+  return j->max_run;
+}
+// true = sa_probe_general_kernel was queued for `right` and *t describes its slot.  The rule is the header's
+// (sqlrs_hash_join_set_async_general): sa_probe_try's conditions without "Inner" and "unique build keys", plus the output bound.
+static bool sa_probe_general_try(sqlrs_hash_join *j, const sqlrs_batch_t *right, sqlrs_ticket *t) {
+  Ctx *ctx = j->ctx;
+  if (!j->async_general) return false;
+  const char *off_e = hook("SQLRS_ASYNC_FAST"); // test hook, read per call: 0 = every batch through the synchronous operator
+  if (off_e && off_e[0] == '0') return false;
+  if (j->has_filter || !j->exact || j->comp.on || j->lkeys.size() != 1 || j->rkeys[0].nodes.size() != 1 ||
+      j->rkeys[0].nodes[0].op != SQLRS_EXPR_INPUT_REF || !right || right->num_rows < 0 || right->num_rows > (int64_t)SA_MAX_ROWS)
+    return false;
+  const int kc = j->rkeys[0].nodes[0].index;
+  if (kc < 0 || kc >= right->num_columns) return false;
+  const sqlrs_column_t &kcol = right->columns[kc];
+  if (kcol.dtype != j->key_dtype || (kcol.validity && kcol.null_count != 0)) return false; // (NULL probe keys match NULL build keys: the general route)
+  if (kcol.dtype != SQLRS_INT64 && kcol.dtype != SQLRS_FLOAT64 && kcol.dtype != SQLRS_INT32) return false;
+  const int nleft = (int)j->left.cols.size();
+  if (nleft + right->num_columns > SA_MAX_COLS) return false;
+  int32_t ldt[SA_MAX_COLS];
+  for (int c = 0; c < nleft; c++) {
+    const DCol &lc = j->left.cols[(size_t)c];
+    if ((lc.dtype != SQLRS_INT32 && lc.dtype != SQLRS_INT64 && lc.dtype != SQLRS_FLOAT64) || lc.stride == 0) return false;
+    ldt[c] = lc.dtype;
+  }
+  dense_resolve(j);
+  if (!j->dense) hash_join_ensure_table(j); // (a build side that established itself on the LDS route has its table built here)
+  if (j->unique && j->join_type == SQLRS_JOIN_INNER) return false; // (sa_probe_kernel's own: it declined for a reason that holds here too)
+  const int mode = j->dense ? 0 : (j->dd_table ? 2 : 1);
+  if (mode == 1 && !j->table) return false;
+  if (!j->unique && !j->rows_by_slot) return false;
+  const uint64_t out_rows = (uint64_t)right->num_rows * hash_join_max_run(j);
+  if (out_rows > SA_MAX_OUT_ROWS) return false;
+  SaRing *r = sa_ring(ctx);
+  const int slot = r ? sa_take_slot(r) : -1;
+  if (slot < 0) return false;
+  SaProbeGenParams p;
+  if (!sa_stage_input(right, r->in_area(slot), &p.lay, nleft, ldt, false, (uint32_t)out_rows)) { // (the byte bound: checked before anything is written)
+    r->busy[slot] = false;
+    return false;
+  }
+  p.nleft = nleft;
+  p.key_col = kc;
+  p.key_is32 = kcol.dtype == SQLRS_INT32;
+  p.mode = mode;
+  p.unique = j->unique ? 1 : 0;
+  p.outer_right = (j->join_type == SQLRS_JOIN_RIGHT || j->join_type == SQLRS_JOIN_FULL) ? 1 : 0;
+  p.mark = (j->join_type == SQLRS_JOIN_LEFT || j->join_type == SQLRS_JOIN_FULL) ? 1 : 0;
+  p.cap = (uint32_t)out_rows;
+  for (int c = 0; c < SA_MAX_COLS; c++) {
+    p.lvals[c] = c < nleft ? j->left.cols[(size_t)c].values : nullptr;
+    p.lvalid[c] = c < nleft && j->left.cols[(size_t)c].has_nulls() ? j->left.cols[(size_t)c].validity : nullptr;
+  }
+  p.table = j->table ? j->table->as<Slot>() : nullptr;
+  p.mask = j->mask;
+  p.dt = dense_table_of(j);
+  p.dd = j->dd_table ? j->dd_table->as<uint32_t>() : nullptr;
+  p.dup_min = j->dup_min;
+  p.dup_range = j->dup_range;
+  p.rows_by_slot = j->rows_by_slot ? j->rows_by_slot->as<uint32_t>() : nullptr;
+  p.visited = p.mark ? j->visited->as<unsigned long long>() : nullptr;
+  p.in = r->in_area(slot);
+  p.out = r->out_area(slot);
+  p.seq = ++r->seq;
+  if (!j->async_ordered) { // the table, the build columns and the cleared `visited` were queued on the ctx stream: the side streams wait for them, once
+    sa_order_after_ctx(ctx, r);
+    j->async_ordered = true;
+  }
+  sa_enqueue(ctx, r, j, sa_probe_general_launch, p, slot);
+  t->slot = slot;
+  t->seq = p.seq;
+  t->lay = p.lay;
+  return true;
+}
 } // namespace sq
 
 extern "C" {
@@ -1319,15 +1555,24 @@ int sqlrs_hash_join_probe_push_async(sqlrs_hash_join_t *j, const sqlrs_batch_t *
     if (!ticket) fail(SQLRS_ERR_INTERNAL, "push_async: null ticket");
     SQ_HIP(hipSetDevice(ctx->device));
     if (!j->finished) fail(SQLRS_ERR_INTERNAL, "probe before build_finish");
+    j->probe_started = true;
     auto t = std::unique_ptr<sqlrs_ticket>(new sqlrs_ticket());
     t->ctx = ctx;
-    if (!j->empty_build && !sa_probe_try(j, right, t.get())) {
+    if (!j->empty_build && !sa_probe_try(j, right, t.get()) && !sa_probe_general_try(j, right, t.get())) {
       sa_flush(ctx); // (tickets complete in issue order)
       InBatch ib(ctx, right);
       DBatch r = probe_batch(j, ib, nullptr);
       t->done = emit_batch(ctx, std::move(r), SQLRS_MEM_HOST);
     }
     *ticket = t.release();
+  });
+}
+// the switch of the general async probe (sa_probe_general_kernel): before the first probe call of any kind
+int sqlrs_hash_join_set_async_general(sqlrs_hash_join_t *j, int on) {
+  if (!j) return SQLRS_ERR_INTERNAL;
+  return guard(j->ctx, [&] {
+    if (j->probe_started) fail(SQLRS_ERR_INTERNAL, "sqlrs_hash_join_set_async_general: after the first probe call");
+    j->async_general = on != 0;
   });
 }
 } // extern "C"
@@ -1364,6 +1609,7 @@ int sqlrs_hash_join_probe_push_many(sqlrs_hash_join_t *j, int n, const sqlrs_bat
     Ctx *ctx = j->ctx;
     SQ_HIP(hipSetDevice(ctx->device));
     if (!j->finished) fail(SQLRS_ERR_INTERNAL, "probe before build_finish");
+    j->probe_started = true;
     for (int i = 0; i < n; i++) out[i] = nullptr;
     if (n <= 0 || j->empty_build) return;
     if (!j->probe_stage) {
@@ -1436,6 +1682,7 @@ int sqlrs_hash_join_probe_indices(sqlrs_hash_join_t *j, const sqlrs_batch_t *rig
   return guard(j->ctx, [&] {
     SQ_HIP(hipSetDevice(j->ctx->device));
     if (!j->finished) fail(SQLRS_ERR_INTERNAL, "probe before build_finish");
+    j->probe_started = true;
     *out = nullptr;
     if (j->empty_build) return;
     InBatch ib(j->ctx, right);
@@ -1471,6 +1718,9 @@ int sqlrs_hash_join_finish(sqlrs_hash_join_t *j, int out_mem, sqlrs_batch_t **ou
     if (j->empty_build) return;
     if (j->join_type != SQLRS_JOIN_LEFT && j->join_type != SQLRS_JOIN_FULL) return;
     Ctx *ctx = j->ctx;
+    // the general async probe kernels mark `visited` on the ring's side streams: what is pending is launched and the side
+    // streams are waited for — with tickets still outstanding too (their batches stay in their slots until they are waited for)
+    if (j->async_ordered) sa_drain(ctx);
     Selection sel = selection_from_clear_bits(ctx, j->visited->as<uint64_t>(), j->nB); // :298-301
     DBatch b;
     b.rows = sel.count;

@@ -87,6 +87,11 @@ struct sqlrs_hash_join {
   // probe batch that cannot take the LDS route asks for it (`table_built` stays false until then)
   bool lds_first = false;
   bool async_ordered = false; // the async path's side streams have been ordered behind this join's build (small_async.hpp)
+  // sqlrs_hash_join_set_async_general: probe_push_async also takes outer joins and duplicate build keys in one launch per batch
+  // (sa_probe_general_kernel, join.hip).  `max_run` = M, the most build rows that share one key (0: not computed yet; rows with
+  // a NULL key count as sharing one) — what bounds the rows a batch can emit; `probe_started`: a probe call of any kind was made
+  bool async_general = false, probe_started = false;
+  uint32_t max_run = 0;
 };
 
 // builds the deferred hash table of a `lazy_table` join (join.hip); no-op otherwise

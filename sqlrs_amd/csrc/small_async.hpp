@@ -13,9 +13,13 @@
 //   * `wait` polls the header's sequence number (system-scope release store behind `__threadfence_system`), falling
 //     back to a stream synchronisation when it does not show up, and copies the rows into an ordinary HOST batch.
 // Anything the fast path does not take — predicates that read a Boolean / Utf8 column or need more than 24 nodes, Utf8
-// columns around a join, more than 4096 rows, DEVICE input,
-// duplicate build keys, join filters, outer joins — runs the synchronous operator inside push_async and parks the finished
-// batch in the ticket: same results, same one-output-per-input rule, no speed-up.
+// columns around a join, more than 4096 rows, DEVICE input, join filters, NULL probe keys, composite or hash-only join keys,
+// duplicate build keys and outer joins (unless the join's switch is on, next paragraph) — runs the synchronous operator
+// inside push_async and parks the finished batch in the ticket: same results, same one-output-per-input rule, no speed-up.
+// sqlrs_hash_join_set_async_general(j, 1): Left / Right / Full joins and build sides with duplicate keys take ONE launch per
+// batch as well (sa_probe_general_kernel, join.hip) — a batch of `rows` rows against a build side whose most frequent key
+// has M rows emits at most rows x M joined rows, and it is taken when rows x M <= SA_MAX_OUT_ROWS and the output columns
+// laid out for rows x M rows fit the slot's output area; the host decides before it takes a slot, nothing overflows.
 #pragma once
 
 #include <cstring>
@@ -27,6 +31,7 @@ namespace sq {
 constexpr int SA_SLOTS = 32, SA_MAX_COLS = 12;
 constexpr uint32_t SA_MAX_ROWS = 4096, SA_NONE = 0xffffffffu;
 constexpr size_t SA_AREA = 512 * 1024; // bytes of a slot's input area and of its output area
+constexpr uint32_t SA_MAX_OUT_ROWS = 16384; // rows one batch of the general probe kernel may emit (rows x M, see above)
 
 struct SaHeader { // at the start of a slot's output area
   unsigned long long seq; // written LAST by the kernel: the ticket's sequence number
@@ -105,10 +110,11 @@ template <class P> inline void sa_enqueue(Ctx *ctx, SaRing *r, const void *owner
 }
 
 // Lays `in` (HOST columns of int32 / int64 / float64 — and Utf8 when `allow_utf8` — <= SA_MAX_ROWS rows) out in `area` and describes it in `lay`;
-// `first_out_col` output columns are reserved in front of the batch's own (the join's build columns).  false = not a batch
-// for the fast path (nothing written that matters).
+// `first_out_col` output columns are reserved in front of the batch's own (the join's build columns).  `out_rows`: the rows
+// the OUTPUT columns and their bitmaps are laid out for (SA_NONE: as many as the batch has; more for a kernel that emits more
+// rows than it reads — fixed-width columns only).  false = not a batch for the fast path (nothing written that matters).
 bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int first_out_col, const int32_t *front_dtypes,
-                    bool allow_utf8 = false);
+                    bool allow_utf8 = false, uint32_t out_rows = SA_NONE);
 
 // ---- a postfix program over the batch's fixed-width columns, evaluated per row INSIDE the one-launch kernels -----------------
 // BoundExpr::eval_column (evaluator.rs:13-28, array_compute.rs:70-90) restated for one row: the same arithmetic (integers wrap,
