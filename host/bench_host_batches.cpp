@@ -442,7 +442,13 @@ static int bench_project(int argc, char **argv) {
 // sqlrs_hash_join_probe_push_async with sqlrs_hash_join_set_async_general off (the synchronous operator inside push_async) and
 // on (one launch per batch), DEPTH tickets in flight.  The off and on runs alternate; best of 2 after a warm-up each; the
 // joined rows (tail batch of Left / Full included) of the three paths must agree.
-static int bench_probe_general(int argc, char **argv) {
+//
+// ./bench_host_batches probe_utf8 [the same arguments]
+// The same with one Utf8 column of 8-16 byte strings on each side (build: chosen by the key; probe: by the probe key, each
+// batch's offsets a window into one array, so offsets[0] != 0).  sqlrs_hash_join_set_async_general is on in both push_async
+// paths; what alternates is sqlrs_hash_join_set_async_utf8: off = the synchronous operator inside push_async (today's
+// behaviour with a Utf8 column around the join), on = one launch per batch.
+static int bench_probe_general(int argc, char **argv, bool utf8) {
   const int64_t n = argc > 2 ? (int64_t)std::atof(argv[2]) : 20000000, nB = argc > 3 ? (int64_t)std::atof(argv[3]) : 1000000;
   const int64_t B = argc > 4 ? std::atoll(argv[4]) : 1024;
   const char *jname = argc > 5 ? argv[5] : "left";
@@ -465,11 +471,30 @@ static int bench_probe_general(int argc, char **argv) {
     fk[(size_t)i] = (int64_t)(splitmix64(0xF1, (uint64_t)i) % (uint64_t)(nkeys + nkeys / 4));
     fv[(size_t)i] = (double)(splitmix64(0xF2, (uint64_t)i) >> 11) * (1.0 / 9007199254740992.0);
   }
+  // Utf8: key k carries 8 + k % 9 bytes of the letter 'a' + k % 26 (build) / 'A' + k % 26 (probe)
+  std::vector<int32_t> doff, foff;
+  std::vector<char> dbytes, fbytes;
+  auto strings = [](const std::vector<int64_t> &keys, char first, std::vector<int32_t> &off, std::vector<char> &bytes) {
+    off.resize(keys.size() + 1);
+    off[0] = 0;
+    for (size_t i = 0; i < keys.size(); i++) off[i + 1] = off[i] + 8 + (int32_t)(keys[i] % 9);
+    bytes.resize((size_t)off[keys.size()] + 1);
+    for (size_t i = 0; i < keys.size(); i++) std::memset(bytes.data() + off[i], first + (int)(keys[i] % 26), (size_t)(off[i + 1] - off[i]));
+  };
+  if (utf8) {
+    if (n * 16 > 2000000000ll) {
+      std::printf("{\"error\": \"probe_utf8: at most 1.25e8 probe rows\"}\n");
+      return 2;
+    }
+    strings(dk, 'a', doff, dbytes);
+    strings(fk, 'A', foff, fbytes);
+  }
+  const int ncl = utf8 ? 3 : 2; // columns per side
   sqlrs_expr_node_t k0{};
   k0.op = SQLRS_EXPR_INPUT_REF;
   k0.index = 0;
   sqlrs_expr_t key{&k0, 1, 0};
-  const int32_t right_dtypes[2] = {SQLRS_INT64, SQLRS_FLOAT64};
+  const int32_t right_dtypes[3] = {SQLRS_INT64, SQLRS_FLOAT64, SQLRS_UTF8};
   const int DEPTH = 8;
   const int64_t nb = (n + B - 1) / B;
   double best[3] = {1e30, 1e30, 1e30}; // push, push_async switch off, push_async switch on
@@ -478,14 +503,19 @@ static int bench_probe_general(int argc, char **argv) {
   auto run = [&](int path, int rep) -> int { // 0 ok
     auto t0 = std::chrono::steady_clock::now();
     sqlrs_hash_join_t *j = nullptr;
-    CHECK(sqlrs_hash_join_create(ctx, jt, 1, &key, &key, nullptr, 2, right_dtypes, &j));
-    if (path == 2) CHECK(sqlrs_hash_join_set_async_general(j, 1));
-    sqlrs_column_t lc[2];
+    CHECK(sqlrs_hash_join_create(ctx, jt, 1, &key, &key, nullptr, ncl, right_dtypes, &j));
+    if (path == 2 || (utf8 && path == 1)) CHECK(sqlrs_hash_join_set_async_general(j, 1));
+    if (utf8 && path == 2) CHECK(sqlrs_hash_join_set_async_utf8(j, 1));
+    sqlrs_column_t lc[3];
     host_col(lc[0], SQLRS_INT64, dk.data(), nB);
     host_col(lc[1], SQLRS_INT64, dp.data(), nB);
+    if (utf8) {
+      host_col(lc[2], SQLRS_UTF8, dbytes.data(), nB);
+      lc[2].offsets = doff.data();
+    }
     sqlrs_batch_t lb{};
     lb.num_rows = nB;
-    lb.num_columns = 2;
+    lb.num_columns = ncl;
     lb.columns = lc;
     CHECK(sqlrs_hash_join_build_push(j, &lb));
     CHECK(sqlrs_hash_join_build_finish(j));
@@ -493,12 +523,22 @@ static int bench_probe_general(int argc, char **argv) {
     auto consume = [&](sqlrs_batch_t *o) { // a matched row carries payload 3 * key + 1 beside the probe row's key
       if (!o) return;
       if (rep == 0 && o->num_rows) {
-        const int64_t *p = (const int64_t *)o->columns[1].values, *rk = (const int64_t *)o->columns[2].values;
+        const int64_t *p = (const int64_t *)o->columns[1].values, *rk = (const int64_t *)o->columns[ncl].values;
         const uint8_t *pv = (const uint8_t *)o->columns[1].validity;
         for (int64_t r = 0; r < o->num_rows; r += 97) {
           const bool matched = rk[r] < nkeys;
           const bool valid = !pv || !o->columns[1].null_count || ((pv[r >> 3] >> (r & 7)) & 1);
           ok = ok && matched == valid && (!matched || p[r] == 3 * rk[r] + 1);
+          for (int side = 0; utf8 && side < 2; side++) { // the strings: length and letter by the key, first and last byte
+            const sqlrs_column_t &sc = o->columns[side ? 2 * ncl - 1 : 2];
+            const int32_t *so = (const int32_t *)sc.offsets;
+            const char *sb = (const char *)sc.values;
+            const uint8_t *sv = (const uint8_t *)sc.validity;
+            const bool svalid = !sv || !sc.null_count || ((sv[r >> 3] >> (r & 7)) & 1);
+            const int32_t len = so[r + 1] - so[r], want = (side || matched) ? 8 + (int32_t)(rk[r] % 9) : 0;
+            const char letter = (char)((side ? 'A' : 'a') + (int)(rk[r] % 26));
+            ok = ok && svalid == (side || matched) && len == want && (!want || (sb[so[r]] == letter && sb[so[r + 1] - 1] == letter));
+          }
         }
       }
       got += o->num_rows;
@@ -513,12 +553,16 @@ static int bench_probe_general(int argc, char **argv) {
       }
       if (b >= nb) continue;
       const int64_t lo = b * B, m = std::min<int64_t>(B, n - lo);
-      sqlrs_column_t rc[2];
+      sqlrs_column_t rc[3];
       host_col(rc[0], SQLRS_INT64, fk.data() + lo, m);
       host_col(rc[1], SQLRS_FLOAT64, fv.data() + lo, m);
+      if (utf8) {
+        host_col(rc[2], SQLRS_UTF8, fbytes.data(), m);
+        rc[2].offsets = foff.data() + lo;
+      }
       sqlrs_batch_t rb{};
       rb.num_rows = m;
-      rb.num_columns = 2;
+      rb.num_columns = ncl;
       rb.columns = rc;
       if (path) {
         CHECK(sqlrs_hash_join_probe_push_async(j, &rb, &q[(size_t)(b % DEPTH)]));
@@ -546,22 +590,25 @@ static int bench_probe_general(int argc, char **argv) {
     for (int path = 1; path <= 2; path++)
       if (run(path, rep)) return 1;
   ok = ok && joined[0] == joined[1] && joined[1] == joined[2] && joined[0] > 0;
-  std::printf("{\"mode\": \"probe_general\", \"join\": \"%s\", \"dup\": %lld, \"probe_rows\": %lld, \"build_rows\": %lld, \"batch_rows\": %lld, "
+  std::printf("{\"mode\": \"%s\", \"join\": \"%s\", \"dup\": %lld, \"probe_rows\": %lld, \"build_rows\": %lld, \"batch_rows\": %lld, "
               "\"joined\": %lld, \"depth\": %d, \"ms_push\": %.1f, \"Mrows_s_push\": %.1f, \"ms_push_async_off\": %.1f, \"Mrows_s_push_async_off\": %.1f, "
               "\"ms_push_async_on\": %.1f, \"Mrows_s_push_async_on\": %.1f, \"on_over_off\": %.2f, \"check\": \"%s\", \"note\": \"native caller "
               "(C ABI): build side one host batch (every key %lld times), probe side pageable %lld-row host batches (a fifth of the keys "
               "without partner), joined batches on the host; push = sqlrs_hash_join_probe_push per batch, push_async_off / _on = "
-              "sqlrs_hash_join_probe_push_async with sqlrs_hash_join_set_async_general 0 / 1 (alternating runs); Mrows/s = probe rows; "
+              "sqlrs_hash_join_probe_push_async with %s 0 / 1 (alternating runs); Mrows/s = probe rows; "
               "build included; best of 2 after a warm-up\"}\n",
-              jname, (long long)dup, (long long)n, (long long)nB, (long long)B, (long long)joined[0], DEPTH, best[0], (double)n / best[0] / 1e3,
+              utf8 ? "probe_utf8" : "probe_general", jname, (long long)dup, (long long)n, (long long)nB, (long long)B, (long long)joined[0], DEPTH, best[0], (double)n / best[0] / 1e3,
               best[1], (double)n / best[1] / 1e3, best[2], (double)n / best[2] / 1e3, best[1] / best[2], ok ? "OK" : "mismatch", (long long)dup,
-              (long long)B);
+              (long long)B,
+              utf8 ? "one Utf8 column of 8-16 byte strings per side, sqlrs_hash_join_set_async_general 1 and sqlrs_hash_join_set_async_utf8"
+                   : "sqlrs_hash_join_set_async_general");
   sqlrs_ctx_destroy(ctx);
   return ok ? 0 : 1;
 }
 
 int main(int argc, char **argv) {
-  if (argc > 1 && std::strcmp(argv[1], "probe_general") == 0) return bench_probe_general(argc, argv);
+  if (argc > 1 && std::strcmp(argv[1], "probe_general") == 0) return bench_probe_general(argc, argv, false);
+  if (argc > 1 && std::strcmp(argv[1], "probe_utf8") == 0) return bench_probe_general(argc, argv, true);
   if (argc > 1 && std::strcmp(argv[1], "filter") == 0) return bench_filter(argc, argv);
   if (argc > 1 && std::strcmp(argv[1], "project") == 0) return bench_project(argc, argv);
   if (argc > 1 && std::strcmp(argv[1], "probe") == 0) return bench_probe(argc, argv);

@@ -356,6 +356,31 @@ int sqlrs_hash_join_probe_push_async(sqlrs_hash_join_t *j, const sqlrs_batch_t *
  * inside push_async, as with the switch off.  Left / Full: sqlrs_hash_join_finish may be called with tickets still
  * outstanding; it waits for the queued probe kernels (which mark the visited build rows) before it reads the marks. */
 int sqlrs_hash_join_set_async_general(sqlrs_hash_join_t *j, int on);
+/* on != 0: both one-launch kernels of sqlrs_hash_join_probe_push_async also carry Utf8 PAYLOAD columns, on the build side
+ * and in the probe batch.  Default 0: exactly today's behaviour.  Calling rules as for sqlrs_hash_join_set_async_general
+ * (after create, before the first probe call of any kind; later: SQLRS_ERR_INTERNAL); the contract of probe_push_async is
+ * unchanged.  The key column stays int32 / int64 / float64.
+ *
+ * Eligibility of a probe batch with the switch on: every condition of the fast path of probe_push_async — or of the
+ * general path above when sqlrs_hash_join_set_async_general is on as well — except "fixed-width columns only": any
+ * non-key column of the build side or of the probe batch may be Utf8.  A Utf8 column of the probe batch has non-NULL
+ * `offsets`, offsets[rows] >= offsets[0], and non-NULL `values` when that range is not empty.  Let out_rows = rows on the
+ * Inner / unique route and rows x M on the general route; the batch is eligible iff out_rows <= 16384 and
+ *   64 + sum over the output columns of piece(c) <= 524288 (SA_AREA), where
+ *     a fixed-width column: round64(width x out_rows) + round64(ceil(out_rows / 8)), as above;
+ *     a Utf8 column: round64(4 x (out_rows + 1)) + round64(ceil(out_rows / 8)) + round64(bytes_c), with
+ *       bytes_c = out_rows x Lmax_c for a build column — Lmax_c the largest offsets[i + 1] - offsets[i] of that build
+ *       column, NULL slots included — and
+ *       bytes_c = B_c x (out_rows / rows) for a probe column, B_c = offsets[rows] - offsets[0] (the factor is 1 or M; a
+ *       0-row batch has 0 bytes),
+ *   and the staged input fits 524288 bytes: per probe column round64(width x rows), for Utf8
+ *   round64(4 x (rows + 1)) + round64(B_c), plus round64(ceil(rows / 8) + 8) per column with NULLs.
+ * Lmax_c is computed once per join (one small kernel over the build column's offsets and one fetch) when it is first
+ * needed.  The host decides before it takes a slot; nothing overflows and nothing is re-run (the kernels compare every
+ * column's bytes with its reservation before they store one, and sqlrs_batch_wait reports SQLRS_ERR_INTERNAL should that
+ * ever fail).  Everything else — the bound exceeded, Boolean columns, a Utf8 key, and the rest of the lists above — runs
+ * the synchronous operator inside push_async, as with the switch off. */
+int sqlrs_hash_join_set_async_utf8(sqlrs_hash_join_t *j, int on);
 /* The index-pair form of one probe batch, before any gather: 2 columns
  * (UINT64 left index, nullable; UINT32 right index), in the reference's order
  * (probe-row major, build insertion order minor), join filter NOT applied.

@@ -64,14 +64,15 @@ int sa_take_slot(SaRing *r) {
 static uint32_t sa_width(int32_t dtype) { return dtype == SQLRS_INT32 ? 4u : (dtype == SQLRS_INT64 || dtype == SQLRS_FLOAT64) ? 8u : 0u; }
 
 bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int first_out_col, const int32_t *front_dtypes, bool allow_utf8,
-                    uint32_t out_rows) {
+                    uint32_t out_rows, const uint64_t *front_bytes) {
   if (!in || in->num_rows < 0 || in->num_rows > (int64_t)SA_MAX_ROWS || in->num_columns <= 0 ||
       in->num_columns + first_out_col > SA_MAX_COLS)
     return false;
   const uint32_t rows = (uint32_t)in->num_rows, vbytes = (rows + 7) / 8;
   if (out_rows == SA_NONE) out_rows = rows;
-  if (out_rows > SA_MAX_OUT_ROWS || (allow_utf8 && out_rows != rows)) return false;
+  if (out_rows > SA_MAX_OUT_ROWS) return false;
   const uint32_t out_vbytes = (out_rows + 7) / 8;
+  const uint64_t utf8_mult = out_rows == rows ? 1 : (rows ? out_rows / rows : 0); // (a batch's own Utf8 bytes: each row at most this often)
   for (int c = 0; c < in->num_columns; c++) {
     const sqlrs_column_t &col = in->columns[c];
     if (col.mem != SQLRS_MEM_HOST || col.length != in->num_rows) return false;
@@ -90,14 +91,20 @@ bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int f
     d.dtype = c < first_out_col ? front_dtypes[c] : in->columns[c - first_out_col].dtype;
     const bool utf8 = d.dtype == SQLRS_UTF8;
     d.width = utf8 ? 4u : sa_width(d.dtype);
-    if (!d.width) return false;
+    if (!d.width || (utf8 && c < first_out_col && !front_bytes)) return false;
     d.in_off = d.in_voff = d.in_data = d.out_data = SA_NONE;
-    d.data_base = 0;
-    const size_t nval = utf8 ? (size_t)rows + 1 : rows, nout = utf8 ? nval : out_rows;
+    d.data_base = d.out_cap = 0;
+    const size_t nval = utf8 ? (size_t)rows + 1 : rows, nout = utf8 ? (size_t)out_rows + 1 : out_rows;
     d.out_off = (uint32_t)out_at;
     out_at = up64(out_at + (size_t)d.width * nout);
     d.out_voff = (uint32_t)out_at;
     out_at = up64(out_at + out_vbytes);
+    if (utf8 && c < first_out_col) { // a build column: its bytes stay where they are, the output's are reserved as the caller says
+      if (front_bytes[c] > SA_AREA) return false;
+      d.out_data = (uint32_t)out_at;
+      d.out_cap = (uint32_t)front_bytes[c];
+      out_at = up64(out_at + (size_t)front_bytes[c]);
+    }
     if (c >= first_out_col) {
       const sqlrs_column_t &col = in->columns[c - first_out_col];
       d.in_off = (uint32_t)in_at;
@@ -111,8 +118,10 @@ bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int f
         d.data_base = (uint32_t)col.offsets[0];
         d.in_data = (uint32_t)in_at;
         in_at = up64(in_at + nbytes);
+        if (nbytes * utf8_mult > SA_AREA) return false;
         d.out_data = (uint32_t)out_at;
-        out_at = up64(out_at + nbytes);
+        d.out_cap = (uint32_t)(nbytes * utf8_mult);
+        out_at = up64(out_at + (size_t)d.out_cap);
       }
     }
     if (in_at > SA_AREA || out_at > SA_AREA) return false;
@@ -241,7 +250,8 @@ int sqlrs_batch_wait(sqlrs_ticket_t *ticket, sqlrs_batch_t **out) {
       for (int i = 0; i < SA_STREAMS; i++) SQ_HIP(hipStreamSynchronize(r->side[i]));
       if (__atomic_load_n(&h->seq, __ATOMIC_ACQUIRE) != ticket->seq) fail(SQLRS_ERR_DEVICE, "batch_wait: the batch's kernel left no result");
     }
-    if (h->pad == 2) fail(SQLRS_ERR_INTERNAL, "batch_wait: the probe kernel met more joined rows than its slot was laid out for");
+    if (h->pad == 2) fail(SQLRS_ERR_INTERNAL, "batch_wait: the probe kernel met more joined rows than its slot was laid out for (a wrong M), or more bytes of a Utf8 column than "
+                                                   "were reserved for it (a wrong Lmax)");
     if (h->pad) fail(SQLRS_ERR_ARROW, "Divide by zero error"); // (what the synchronous evaluator raises at the push, expr.hip)
     const SaLayout &lay = ticket->lay;
     const uint8_t *oa = r->out_area(ticket->slot);

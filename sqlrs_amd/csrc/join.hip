@@ -1204,8 +1204,17 @@ struct SaProbeParams {
   uint8_t *out;
   unsigned long long seq;
 };
-__global__ __launch_bounds__(1024) void sa_probe_kernel(SaGroup<SaProbeParams> grp) {
-  const SaProbeParams &p = grp.p[blockIdx.x]; // (one workgroup per batch of the group)
+// sqlrs_hash_join_set_async_utf8: the same with Utf8 payload columns on either side (UTF8 = true; batches without one keep the
+// instantiation they always had).  Per Utf8 column the Filter's scheme (ops.hip, sa_filter_kernel): the kept rows' lengths by
+// output position in LDS, a block exclusive scan that is the output offsets, then the bytes row by row — from the build
+// column in HBM (loffs / lvals by the build row) or from the batch's own bytes in the slot.  The column's bytes are compared
+// with what the host reserved (SaCol::out_cap) before one of them is stored.
+struct SaProbeUtf8Params : SaProbeParams {
+  const int32_t *loffs[SA_MAX_COLS]; // build columns: the offsets of a Utf8 column (lvals = its bytes) or null
+};
+template <bool UTF8>
+__global__ __launch_bounds__(1024) void sa_probe_kernel(SaGroup<std::conditional_t<UTF8, SaProbeUtf8Params, SaProbeParams>> grp) {
+  const auto &p = grp.p[blockIdx.x]; // (one workgroup per batch of the group)
   __shared__ uint32_t s_w[17], s_nulls[SA_MAX_COLS];
   __shared__ uint8_t s_v[SA_MAX_ROWS];
   if (threadIdx.x < SA_MAX_COLS) s_nulls[threadIdx.x] = 0;
@@ -1227,12 +1236,77 @@ __global__ __launch_bounds__(1024) void sa_probe_kernel(SaGroup<SaProbeParams> g
         return h != DENSE_EMPTY;
       },
       pos, s_w, &total);
+  [[maybe_unused]] bool failed = false;
   for (int c = 0; c < p.lay.ncols; c++) {
     const SaCol &col = p.lay.c[c];
     const bool left = c < p.nleft;
     const uint8_t *rvalid = !left && col.in_voff != SA_NONE ? p.in + col.in_voff : nullptr;
     const uint64_t *lvalid = left ? p.lvalid[c] : nullptr;
     const uint8_t *src = left ? (const uint8_t *)p.lvals[c] : p.in + col.in_off;
+    if constexpr (UTF8) {
+      if (col.dtype == SQLRS_UTF8) { // (uniform: the layout is a kernel argument)
+        __shared__ uint32_t s_len[SA_MAX_ROWS + 4]; // lengths of the kept rows in output order, then their exclusive prefix
+        const int32_t *off = left ? p.loffs[c] : (const int32_t *)(p.in + col.in_off);
+        int32_t *ooff = (int32_t *)(p.out + col.out_off);
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+          if (!((bits >> t) & 1)) continue;
+          const uint32_t r = left ? m[t] : (uint32_t)t * 1024u + threadIdx.x;
+          s_len[pos[t]] = (uint32_t)(off[r + 1] - off[r]);
+          if (lvalid) s_v[pos[t]] = (uint8_t)((lvalid[r >> 6] >> (r & 63)) & 1);
+          else if (rvalid) s_v[pos[t]] = (rvalid[r >> 3] >> (r & 7)) & 1;
+        }
+        __syncthreads();
+        { // thread i owns entries 4 i .. 4 i + 3 of the (<= 4096) lengths
+          uint32_t a[4], sum = 0;
+#pragma unroll
+          for (int q = 0; q < 4; q++) {
+            const uint32_t i = threadIdx.x * 4 + q;
+            a[q] = i < total ? s_len[i] : 0u;
+            sum += a[q];
+          }
+          const uint32_t inc = wave_iscan_u32(sum);
+          if (lane_id() == 63) s_w[wave_id()] = inc;
+          __syncthreads();
+          uint32_t base = inc - sum, all = 0;
+#pragma unroll
+          for (int q = 0; q < 16; q++) {
+            const uint32_t wsum = s_w[q];
+            base += q < wave_id() ? wsum : 0;
+            all += wsum;
+          }
+          failed = all > col.out_cap; // (uniform; cannot happen while the host's reservation is right)
+          if (!failed) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+              const uint32_t i = threadIdx.x * 4 + q;
+              if (i <= total) { // (entry `total` = the end of the last string)
+                s_len[i] = base;
+                ooff[i] = (int32_t)base;
+              }
+              base += a[q];
+            }
+            if (total == SA_MAX_ROWS && threadIdx.x == 1023) ooff[SA_MAX_ROWS] = (int32_t)base; // (a full batch kept whole: its end offset has no owner above)
+          }
+        }
+        __syncthreads();
+        if (failed) break; // (nothing of this column's bytes is stored, zero rows are published, the wait reports it)
+        const uint8_t *bytes = left ? (const uint8_t *)p.lvals[c] : p.in + col.in_data;
+        const uint32_t data_base = left ? 0u : col.data_base;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+          if (!((bits >> t) & 1)) continue;
+          const uint32_t r = left ? m[t] : (uint32_t)t * 1024u + threadIdx.x;
+          const uint32_t beg = (uint32_t)off[r], len = (uint32_t)off[r + 1] - beg;
+          const uint8_t *from = bytes + (beg - data_base);
+          uint8_t *dst = p.out + col.out_data + s_len[pos[t]];
+          for (uint32_t b = 0; b < len; b++) dst[b] = from[b];
+        }
+        if (lvalid || rvalid) sa_pack_validity(s_v, total, p.out + col.out_voff, &s_nulls[c]);
+        else __syncthreads(); // (s_len is reused by the next Utf8 column)
+        continue;
+      }
+    }
 #pragma unroll
     for (int t = 0; t < 4; t++) {
       if (!((bits >> t) & 1)) continue;
@@ -1244,13 +1318,73 @@ __global__ __launch_bounds__(1024) void sa_probe_kernel(SaGroup<SaProbeParams> g
     }
     if (lvalid || rvalid) sa_pack_validity(s_v, total, p.out + col.out_voff, &s_nulls[c]);
   }
-  sa_publish((SaHeader *)p.out, p.seq, total, s_nulls, p.lay.ncols);
+  if constexpr (UTF8) {
+    __shared__ uint32_t s_err;
+    if (threadIdx.x == 0) s_err = failed ? 2u : 0u;
+    sa_publish((SaHeader *)p.out, p.seq, failed ? 0u : total, s_nulls, p.lay.ncols, &s_err);
+  } else
+    sa_publish((SaHeader *)p.out, p.seq, total, s_nulls, p.lay.ncols);
 }
-static void sa_probe_launch(SaRing *r, Ctx *ctx) {
-  SaGroup<SaProbeParams> g;
-  for (int i = 0; i < r->pend_n; i++) std::memcpy(&g.p[i], r->pend_buf + (size_t)i * SA_PARAM_MAX, sizeof(SaProbeParams));
-  sa_probe_kernel<<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g);
+template <bool UTF8> static void sa_probe_launch(SaRing *r, Ctx *ctx) {
+  using P = std::conditional_t<UTF8, SaProbeUtf8Params, SaProbeParams>;
+  SaGroup<P> g;
+  for (int i = 0; i < r->pend_n; i++) std::memcpy(&g.p[i], r->pend_buf + (size_t)i * SA_PARAM_MAX, sizeof(P));
+  sa_probe_kernel<UTF8><<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g);
   SQ_HIP(hipGetLastError());
+}
+// Lmax of every Utf8 build column: the longest string in bytes, NULL slots included — what one output row can cost at the most
+__global__ void sa_utf8_lmax_kernel(const int32_t *__restrict__ off, int64_t n, uint32_t *__restrict__ out) {
+  uint32_t m = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    m = max(m, (uint32_t)(off[i + 1] - off[i]));
+  for (int s = 32; s >= 1; s >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, s, 64));
+  if (lane_id() == 0 && m) atomicMax(out, m);
+}
+// once per join, when the first batch needs it: one kernel and one fetch per Utf8 build column
+static const std::vector<int64_t> &hash_join_utf8_lmax(sqlrs_hash_join *j) {
+  if (!j->utf8_lmax_known) {
+    Ctx *ctx = j->ctx;
+    j->utf8_lmax.assign(j->left.cols.size(), -1);
+    for (size_t c = 0; c < j->left.cols.size(); c++) {
+      const DCol &lc = j->left.cols[c];
+      if (lc.dtype != SQLRS_UTF8) continue;
+      const int64_t n = lc.length;
+      BufP out = ctx->alloc_zero(8);
+      if (n > 0) {
+        const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 256 * 4), 4 * (int64_t)ctx->num_cus));
+        sa_utf8_lmax_kernel<<<dim3(blocks), dim3(256), 0, ctx->stream>>>(lc.offsets, n, out->as<uint32_t>());
+        SQ_HIP(hipGetLastError());
+      }
+      j->utf8_lmax[c] = (int64_t)ctx->fetch_value(out->as<uint32_t>());
+    }
+    j->utf8_lmax_known = true;
+  }
+  return j->utf8_lmax;
+}
+// the build columns of a batch for the async kernels: dtypes, and whether they are columns the kernels carry.  *any_utf8: one is Utf8
+static bool sa_probe_build_cols(sqlrs_hash_join *j, int32_t *ldt, bool *any_utf8) {
+  const int nleft = (int)j->left.cols.size();
+  for (int c = 0; c < nleft; c++) {
+    const DCol &lc = j->left.cols[(size_t)c];
+    if (lc.stride == 0) return false;
+    if (lc.dtype == SQLRS_UTF8) {
+      if (!j->async_utf8 || !lc.offsets) return false;
+      *any_utf8 = true;
+    } else if (lc.dtype != SQLRS_INT32 && lc.dtype != SQLRS_INT64 && lc.dtype != SQLRS_FLOAT64)
+      return false;
+    ldt[c] = lc.dtype;
+  }
+  return true;
+}
+static bool sa_batch_has_utf8(const sqlrs_batch_t *b) {
+  for (int c = 0; c < b->num_columns; c++)
+    if (b->columns[c].dtype == SQLRS_UTF8) return true;
+  return false;
+}
+// bytes to reserve per Utf8 build column for `out_rows` output rows (others 0)
+static void sa_probe_front_bytes(sqlrs_hash_join *j, uint64_t out_rows, uint64_t *front_bytes) {
+  const std::vector<int64_t> &lmax = hash_join_utf8_lmax(j);
+  for (size_t c = 0; c < lmax.size(); c++) front_bytes[c] = lmax[c] > 0 ? out_rows * (uint64_t)lmax[c] : 0;
 }
 // true = the kernel above was queued for `right` and *t describes its slot
 static bool sa_probe_try(sqlrs_hash_join *j, const sqlrs_batch_t *right, sqlrs_ticket *t) {
@@ -1268,19 +1402,19 @@ static bool sa_probe_try(sqlrs_hash_join *j, const sqlrs_batch_t *right, sqlrs_t
   const int nleft = (int)j->left.cols.size();
   if (nleft + right->num_columns > SA_MAX_COLS) return false;
   int32_t ldt[SA_MAX_COLS];
-  for (int c = 0; c < nleft; c++) {
-    const DCol &lc = j->left.cols[(size_t)c];
-    if ((lc.dtype != SQLRS_INT32 && lc.dtype != SQLRS_INT64 && lc.dtype != SQLRS_FLOAT64) || lc.stride == 0) return false;
-    ldt[c] = lc.dtype;
-  }
+  bool utf8 = false;
+  if (!sa_probe_build_cols(j, ldt, &utf8)) return false;
+  if (j->async_utf8 && !utf8) utf8 = sa_batch_has_utf8(right);
   dense_resolve(j);
   if (!j->dense) hash_join_ensure_table(j);
   if (!j->unique || (!j->dense && !j->table)) return false;
+  uint64_t front_bytes[SA_MAX_COLS] = {};
+  if (utf8 && right->num_rows >= 0 && right->num_rows <= (int64_t)SA_MAX_ROWS) sa_probe_front_bytes(j, (uint64_t)right->num_rows, front_bytes);
   SaRing *r = sa_ring(ctx);
   const int slot = r ? sa_take_slot(r) : -1;
   if (slot < 0) return false;
-  SaProbeParams p;
-  if (!sa_stage_input(right, r->in_area(slot), &p.lay, nleft, ldt)) {
+  SaProbeUtf8Params p;
+  if (!sa_stage_input(right, r->in_area(slot), &p.lay, nleft, ldt, utf8, SA_NONE, utf8 ? front_bytes : nullptr)) { // (the byte bound: checked before anything is written)
     r->busy[slot] = false;
     return false;
   }
@@ -1291,6 +1425,7 @@ static bool sa_probe_try(sqlrs_hash_join *j, const sqlrs_batch_t *right, sqlrs_t
   for (int c = 0; c < SA_MAX_COLS; c++) {
     p.lvals[c] = c < nleft ? j->left.cols[(size_t)c].values : nullptr;
     p.lvalid[c] = c < nleft && j->left.cols[(size_t)c].has_nulls() ? j->left.cols[(size_t)c].validity : nullptr;
+    p.loffs[c] = c < nleft && j->left.cols[(size_t)c].dtype == SQLRS_UTF8 ? j->left.cols[(size_t)c].offsets : nullptr;
   }
   p.table = j->table ? j->table->as<Slot>() : nullptr;
   p.mask = j->mask;
@@ -1302,7 +1437,8 @@ static bool sa_probe_try(sqlrs_hash_join *j, const sqlrs_batch_t *right, sqlrs_t
     sa_order_after_ctx(ctx, r);
     j->async_ordered = true;
   }
-  sa_enqueue(ctx, r, j, sa_probe_launch, p, slot);
+  if (utf8) sa_enqueue(ctx, r, j, sa_probe_launch<true>, p, slot);
+  else sa_enqueue(ctx, r, j, sa_probe_launch<false>, (const SaProbeParams &)p, slot);
   t->slot = slot;
   t->seq = p.seq;
   t->lay = p.lay;
@@ -1339,12 +1475,25 @@ struct SaProbeGenParams {
   uint8_t *out;
   unsigned long long seq;
 };
-__global__ __launch_bounds__(1024) void sa_probe_general_kernel(SaGroup<SaProbeGenParams> grp) {
-  const SaProbeGenParams &p = grp.p[blockIdx.x]; // (one workgroup per batch of the group)
+// sqlrs_hash_join_set_async_utf8 (UTF8 = true; batches without a Utf8 column keep the instantiation they always had): inside a
+// 1024-row chunk of output every thread takes its row's length per Utf8 column (a build column: of the build row, 0 for a row
+// without partner; a probe column: of the probe row), a wave scan and the 16 wave totals in s_w give the chunk-local offsets, a
+// running byte base per column (s_ubase, LDS) carries across chunks; the chunk's bytes are compared with what the host
+// reserved (SaCol::out_cap) before one of them is stored.
+struct SaProbeGenUtf8Params : SaProbeGenParams {
+  const int32_t *loffs[SA_MAX_COLS]; // build columns: the offsets of a Utf8 column (lvals = its bytes) or null
+};
+template <bool UTF8>
+__global__ __launch_bounds__(1024) void sa_probe_general_kernel(SaGroup<std::conditional_t<UTF8, SaProbeGenUtf8Params, SaProbeGenParams>> grp) {
+  const auto &p = grp.p[blockIdx.x]; // (one workgroup per batch of the group)
   __shared__ uint32_t s_off[SA_MAX_ROWS], s_start[SA_MAX_ROWS]; // per probe row: first output row; run start / build row / DENSE_EMPTY
   __shared__ uint32_t s_w[16], s_nulls[SA_MAX_COLS], s_err;
+  [[maybe_unused]] __shared__ uint32_t s_ubase[SA_MAX_COLS]; // Utf8: bytes of the column emitted by the chunks so far
+  [[maybe_unused]] bool failed = false;
   const int lane = lane_id(), w = wave_id();
   if (threadIdx.x < SA_MAX_COLS) s_nulls[threadIdx.x] = 0;
+  if constexpr (UTF8)
+    if (threadIdx.x < SA_MAX_COLS) s_ubase[threadIdx.x] = 0;
   if (threadIdx.x == 0) s_err = 0;
   const uint32_t rows = p.lay.rows;
   const SaCol &kc = p.lay.c[p.nleft + p.key_col];
@@ -1421,7 +1570,47 @@ __global__ __launch_bounds__(1024) void sa_probe_general_kernel(SaGroup<SaProbeG
       const uint64_t *lvalid = left ? p.lvalid[c] : nullptr;
       const uint8_t *src = left ? (const uint8_t *)p.lvals[c] : p.in + col.in_off;
       bool valid = true;
-      if (act) {
+      bool is_utf8 = false;
+      if constexpr (UTF8) is_utf8 = col.dtype == SQLRS_UTF8; // (uniform: the layout is a kernel argument)
+      if constexpr (UTF8) {
+        if (is_utf8) {
+          const int32_t *off = left ? p.loffs[c] : (const int32_t *)(p.in + col.in_off);
+          const uint32_t s = left ? brow : r;
+          valid = !act || s != DENSE_EMPTY; // (a probe row without partner: NULL and no bytes in every build column)
+          uint32_t beg = 0, len = 0;
+          if (act && valid) {
+            beg = (uint32_t)off[s];
+            len = (uint32_t)off[s + 1] - beg;
+          }
+          const uint32_t inc = wave_iscan_u32(len);
+          if (lane == 63) s_w[w] = inc;
+          __syncthreads();
+          uint32_t before = 0, all = 0;
+#pragma unroll
+          for (int q = 0; q < 16; q++) {
+            const uint32_t ws = s_w[q];
+            before += q < w ? ws : 0;
+            all += ws;
+          }
+          const uint32_t cbase = s_ubase[c];
+          failed = all > col.out_cap || cbase > col.out_cap - all; // (uniform; cannot happen while the host's reservation is right)
+          if (act && !failed) {
+            const uint32_t at = cbase + before + inc - len;
+            ((int32_t *)(p.out + col.out_off))[o] = (int32_t)at;
+            const uint8_t *from = left ? (const uint8_t *)p.lvals[c] + beg : p.in + col.in_data + (beg - col.data_base);
+            uint8_t *dst = p.out + col.out_data + at;
+            for (uint32_t b = 0; b < len; b++) dst[b] = from[b];
+          }
+          __syncthreads(); // (s_w and s_ubase[c] have been read by everyone: the next column / chunk may write them)
+          if (threadIdx.x == 0) s_ubase[c] = cbase + all;
+          if (failed) break; // (nothing of this chunk's bytes was stored; zero rows are published, the wait reports it)
+          if (act && valid) {
+            if (lvalid) valid = (lvalid[s >> 6] >> (s & 63)) & 1;
+            else if (rvalid) valid = (rvalid[s >> 3] >> (s & 7)) & 1;
+          }
+        }
+      }
+      if (act && !is_utf8) {
         const uint32_t s = left ? brow : r;
         valid = s != DENSE_EMPTY; // (a probe row without partner: NULL in every build column)
         if (col.width == 8) ((uint64_t *)(p.out + col.out_off))[o] = valid ? ((const uint64_t *)src)[s] : 0ull;
@@ -1438,13 +1627,26 @@ __global__ __launch_bounds__(1024) void sa_probe_general_kernel(SaGroup<SaProbeG
         }
       }
     }
+    if constexpr (UTF8)
+      if (failed) break;
+  }
+  if constexpr (UTF8) {
+    __syncthreads();
+    if (failed) {
+      total = 0;
+      if (threadIdx.x == 0) s_err = 2;
+    }
+    if (threadIdx.x == 0) // the end of the last string (zero rows: the one offset there is)
+      for (int c = 0; c < p.lay.ncols; c++)
+        if (p.lay.c[c].dtype == SQLRS_UTF8) ((int32_t *)(p.out + p.lay.c[c].out_off))[total] = (int32_t)(failed ? 0u : s_ubase[c]);
   }
   sa_publish((SaHeader *)p.out, p.seq, total, s_nulls, p.lay.ncols, &s_err);
 }
-static void sa_probe_general_launch(SaRing *r, Ctx *ctx) {
-  SaGroup<SaProbeGenParams> g;
-  for (int i = 0; i < r->pend_n; i++) std::memcpy(&g.p[i], r->pend_buf + (size_t)i * SA_PARAM_MAX, sizeof(SaProbeGenParams));
-  sa_probe_general_kernel<<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g);
+template <bool UTF8> static void sa_probe_general_launch(SaRing *r, Ctx *ctx) {
+  using P = std::conditional_t<UTF8, SaProbeGenUtf8Params, SaProbeGenParams>;
+  SaGroup<P> g;
+  for (int i = 0; i < r->pend_n; i++) std::memcpy(&g.p[i], r->pend_buf + (size_t)i * SA_PARAM_MAX, sizeof(P));
+  sa_probe_general_kernel<UTF8><<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g);
   SQ_HIP(hipGetLastError());
 }
 // M: the most build rows that share one key — the largest Slot.count of the 16-byte-slot table (its NULL-key slot included) or
@@ -1489,11 +1691,9 @@ static bool sa_probe_general_try(sqlrs_hash_join *j, const sqlrs_batch_t *right,
   const int nleft = (int)j->left.cols.size();
   if (nleft + right->num_columns > SA_MAX_COLS) return false;
   int32_t ldt[SA_MAX_COLS];
-  for (int c = 0; c < nleft; c++) {
-    const DCol &lc = j->left.cols[(size_t)c];
-    if ((lc.dtype != SQLRS_INT32 && lc.dtype != SQLRS_INT64 && lc.dtype != SQLRS_FLOAT64) || lc.stride == 0) return false;
-    ldt[c] = lc.dtype;
-  }
+  bool utf8 = false;
+  if (!sa_probe_build_cols(j, ldt, &utf8)) return false;
+  if (j->async_utf8 && !utf8) utf8 = sa_batch_has_utf8(right);
   dense_resolve(j);
   if (!j->dense) hash_join_ensure_table(j); // (a build side that established itself on the LDS route has its table built here)
   if (j->unique && j->join_type == SQLRS_JOIN_INNER) return false; // (sa_probe_kernel's own: it declined for a reason that holds here too)
@@ -1502,11 +1702,13 @@ static bool sa_probe_general_try(sqlrs_hash_join *j, const sqlrs_batch_t *right,
   if (!j->unique && !j->rows_by_slot) return false;
   const uint64_t out_rows = (uint64_t)right->num_rows * hash_join_max_run(j);
   if (out_rows > SA_MAX_OUT_ROWS) return false;
+  uint64_t front_bytes[SA_MAX_COLS] = {};
+  if (utf8) sa_probe_front_bytes(j, out_rows, front_bytes);
   SaRing *r = sa_ring(ctx);
   const int slot = r ? sa_take_slot(r) : -1;
   if (slot < 0) return false;
-  SaProbeGenParams p;
-  if (!sa_stage_input(right, r->in_area(slot), &p.lay, nleft, ldt, false, (uint32_t)out_rows)) { // (the byte bound: checked before anything is written)
+  SaProbeGenUtf8Params p;
+  if (!sa_stage_input(right, r->in_area(slot), &p.lay, nleft, ldt, utf8, (uint32_t)out_rows, utf8 ? front_bytes : nullptr)) { // (the byte bound: checked before anything is written)
     r->busy[slot] = false;
     return false;
   }
@@ -1521,6 +1723,7 @@ static bool sa_probe_general_try(sqlrs_hash_join *j, const sqlrs_batch_t *right,
   for (int c = 0; c < SA_MAX_COLS; c++) {
     p.lvals[c] = c < nleft ? j->left.cols[(size_t)c].values : nullptr;
     p.lvalid[c] = c < nleft && j->left.cols[(size_t)c].has_nulls() ? j->left.cols[(size_t)c].validity : nullptr;
+    p.loffs[c] = c < nleft && j->left.cols[(size_t)c].dtype == SQLRS_UTF8 ? j->left.cols[(size_t)c].offsets : nullptr;
   }
   p.table = j->table ? j->table->as<Slot>() : nullptr;
   p.mask = j->mask;
@@ -1537,7 +1740,8 @@ static bool sa_probe_general_try(sqlrs_hash_join *j, const sqlrs_batch_t *right,
     sa_order_after_ctx(ctx, r);
     j->async_ordered = true;
   }
-  sa_enqueue(ctx, r, j, sa_probe_general_launch, p, slot);
+  if (utf8) sa_enqueue(ctx, r, j, sa_probe_general_launch<true>, p, slot);
+  else sa_enqueue(ctx, r, j, sa_probe_general_launch<false>, (const SaProbeGenParams &)p, slot);
   t->slot = slot;
   t->seq = p.seq;
   t->lay = p.lay;
@@ -1573,6 +1777,14 @@ int sqlrs_hash_join_set_async_general(sqlrs_hash_join_t *j, int on) {
   return guard(j->ctx, [&] {
     if (j->probe_started) fail(SQLRS_ERR_INTERNAL, "sqlrs_hash_join_set_async_general: after the first probe call");
     j->async_general = on != 0;
+  });
+}
+// the switch of the Utf8 payload columns in both async probe kernels: before the first probe call of any kind
+int sqlrs_hash_join_set_async_utf8(sqlrs_hash_join_t *j, int on) {
+  if (!j) return SQLRS_ERR_INTERNAL;
+  return guard(j->ctx, [&] {
+    if (j->probe_started) fail(SQLRS_ERR_INTERNAL, "sqlrs_hash_join_set_async_utf8: after the first probe call");
+    j->async_utf8 = on != 0;
   });
 }
 } // extern "C"

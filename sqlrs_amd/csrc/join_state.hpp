@@ -92,6 +92,10 @@ struct sqlrs_hash_join {
   // a NULL key count as sharing one) — what bounds the rows a batch can emit; `probe_started`: a probe call of any kind was made
   bool async_general = false, probe_started = false;
   uint32_t max_run = 0;
+  // sqlrs_hash_join_set_async_utf8: both async probe kernels carry Utf8 payload columns.  utf8_lmax[c] = the longest string of
+  // build column c in bytes, NULL slots included (-1: not a Utf8 column), computed when the first batch needs it (utf8_lmax_known)
+  bool async_utf8 = false, utf8_lmax_known = false;
+  std::vector<int64_t> utf8_lmax;
 };
 
 // builds the deferred hash table of a `lazy_table` join (join.hip); no-op otherwise

@@ -13,13 +13,19 @@
 //   * `wait` polls the header's sequence number (system-scope release store behind `__threadfence_system`), falling
 //     back to a stream synchronisation when it does not show up, and copies the rows into an ordinary HOST batch.
 // Anything the fast path does not take — predicates that read a Boolean / Utf8 column or need more than 24 nodes, Utf8
-// columns around a join, more than 4096 rows, DEVICE input, join filters, NULL probe keys, composite or hash-only join keys,
+// columns around a join (unless the join's Utf8 switch is on, last paragraph), more than 4096 rows, DEVICE input, join filters, NULL probe keys, composite or hash-only join keys,
 // duplicate build keys and outer joins (unless the join's switch is on, next paragraph) — runs the synchronous operator
 // inside push_async and parks the finished batch in the ticket: same results, same one-output-per-input rule, no speed-up.
 // sqlrs_hash_join_set_async_general(j, 1): Left / Right / Full joins and build sides with duplicate keys take ONE launch per
 // batch as well (sa_probe_general_kernel, join.hip) — a batch of `rows` rows against a build side whose most frequent key
 // has M rows emits at most rows x M joined rows, and it is taken when rows x M <= SA_MAX_OUT_ROWS and the output columns
 // laid out for rows x M rows fit the slot's output area; the host decides before it takes a slot, nothing overflows.
+// sqlrs_hash_join_set_async_utf8(j, 1): both probe kernels also carry Utf8 PAYLOAD columns, build side and probe side (the key
+// stays int32 / int64 / float64): sa_probe_kernel<true> with the Filter's scheme (lengths by output position in LDS, a block scan,
+// a byte copy per row), sa_probe_general_kernel<true> with a scan per 1024-row chunk of output and a running byte base per
+// column.  The host reserves out_rows x Lmax bytes for a build column (Lmax: its longest string, NULL slots included, one kernel
+// and one fetch per join) and B x (out_rows / rows) for a probe column of B bytes, and admits the batch only when that fits the
+// slot; the kernels check every column's bytes against SaCol::out_cap before they store one.
 #pragma once
 
 #include <cstring>
@@ -43,8 +49,10 @@ struct SaCol {
   uint32_t out_off, out_voff; // values / validity bitmap in the output area (always reserved)
   uint32_t width;             // 4 or 8; Utf8: 4 (in_off / out_off are the int32 offsets, rows + 1 of them)
   int32_t dtype;
-  // Utf8 (Filter only): the bytes [offsets[0], offsets[rows]) of the input column sit at in_data; the kept rows' bytes go to out_data
+  // Utf8: the bytes [offsets[0], offsets[rows]) of the input column sit at in_data (a join's build columns: in HBM, in_data
+  // unused); the emitted rows' bytes go to out_data, which has out_cap bytes reserved — the kernel stores none past them
   uint32_t in_data, out_data, data_base; // data_base = offsets[0] of the input column
+  uint32_t out_cap;
 };
 struct SaLayout {
   int ncols = 0;
@@ -112,9 +120,11 @@ template <class P> inline void sa_enqueue(Ctx *ctx, SaRing *r, const void *owner
 // Lays `in` (HOST columns of int32 / int64 / float64 — and Utf8 when `allow_utf8` — <= SA_MAX_ROWS rows) out in `area` and describes it in `lay`;
 // `first_out_col` output columns are reserved in front of the batch's own (the join's build columns).  `out_rows`: the rows
 // the OUTPUT columns and their bitmaps are laid out for (SA_NONE: as many as the batch has; more for a kernel that emits more
-// rows than it reads — fixed-width columns only).  false = not a batch for the fast path (nothing written that matters).
+// rows than it reads — a Utf8 column of the batch then has (its bytes) x (out_rows / rows) reserved: every row emitted equally
+// often at the most).  `front_bytes` (may be null: no Utf8 column in front): the bytes to reserve for the data of front column c
+// when it is Utf8.  false = not a batch for the fast path (nothing written that matters).
 bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int first_out_col, const int32_t *front_dtypes,
-                    bool allow_utf8 = false, uint32_t out_rows = SA_NONE);
+                    bool allow_utf8 = false, uint32_t out_rows = SA_NONE, const uint64_t *front_bytes = nullptr);
 
 // ---- a postfix program over the batch's fixed-width columns, evaluated per row INSIDE the one-launch kernels -----------------
 // BoundExpr::eval_column (evaluator.rs:13-28, array_compute.rs:70-90) restated for one row: the same arithmetic (integers wrap,
