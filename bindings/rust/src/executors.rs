@@ -164,6 +164,10 @@ fn join_keys(cond: &JoinCondition) -> Result<(Vec<BoundExpr>, Vec<BoundExpr>, Op
         JoinCondition::None => Err(ExecutorError::InternalError("HashJoin must has on condition".into())),
     }
 }
+// (This executor polls through the synchronous sqlrs_hash_join_probe_push.  A caller that polls through
+//  sqlrs_hash_join_probe_push_async instead sets the async switches of ffi.rs right after create and before the first probe
+//  call: sqlrs_hash_join_set_async_general, sqlrs_hash_join_set_async_utf8 and, for a JoinCondition::On with a filter,
+//  sqlrs_hash_join_set_async_filter — each takes the join and 0 / 1.)
 impl HipHashJoinExecutor {
     #[try_stream(boxed, ok = RecordBatch, error = ExecutorError)]
     pub async fn execute(self) {

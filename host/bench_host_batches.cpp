@@ -606,7 +606,179 @@ static int bench_probe_general(int argc, char **argv, bool utf8) {
   return ok ? 0 : 1;
 }
 
+
+// ./bench_host_batches probe_filter [rows = 2e7] [build = 1e6] [batch = 1024] [join = inner|left|right|full] [dup = 1|4]
+// The probe stream of probe_general with a join filter, ON l.k = r.k AND l.x > r.v over two float64 payload columns (uniform in
+// [0, 1): about half the pairs pass), through three paths: sqlrs_hash_join_probe_push per batch, and
+// sqlrs_hash_join_probe_push_async with sqlrs_hash_join_set_async_filter off (the synchronous operator inside push_async: what
+// a filtered join always took) and on (one launch per batch, the filter inside the kernel); sqlrs_hash_join_set_async_general
+// is on in both push_async paths.  The off and on runs alternate; best of 2 after a warm-up each.  Its own check: the joined
+// rows of every path (tail batch of Left / Full included) must equal the count the host works out from the keys and the two
+// payload columns, and on every 97th row of the first run a matched row carries l.k = r.k and l.x > r.v.
+// Compiled with -DSQLRS_BENCH_NO_ASYNC_FILTER the one call of the new setter is left out and the on path is not run: the tool
+// then builds against a library that has no such entry point.
+static int bench_probe_filter(int argc, char **argv) {
+  const int64_t n = argc > 2 ? (int64_t)std::atof(argv[2]) : 20000000, nB = argc > 3 ? (int64_t)std::atof(argv[3]) : 1000000;
+  const int64_t B = argc > 4 ? std::atoll(argv[4]) : 1024;
+  const char *jname = argc > 5 ? argv[5] : "inner";
+  const int64_t dup = argc > 6 ? std::max<int64_t>(1, std::atoll(argv[6])) : 1;
+  const int jt = std::strcmp(jname, "left") == 0 ? SQLRS_JOIN_LEFT : std::strcmp(jname, "right") == 0 ? SQLRS_JOIN_RIGHT
+                 : std::strcmp(jname, "full") == 0 ? SQLRS_JOIN_FULL : SQLRS_JOIN_INNER;
+#ifdef SQLRS_BENCH_NO_ASYNC_FILTER
+  const int npaths = 2;
+#else
+  const int npaths = 3;
+#endif
+  sqlrs_ctx_t *ctx = nullptr;
+  if (sqlrs_ctx_create(0, &ctx) != SQLRS_OK) {
+    std::printf("{\"error\": \"no device\"}\n");
+    return 2;
+  }
+  const int64_t nkeys = std::max<int64_t>(1, nB / dup);
+  std::vector<int64_t> dk((size_t)nB), fk((size_t)n);
+  std::vector<double> dx((size_t)nB), fv((size_t)n);
+  auto unit = [](uint64_t seed, uint64_t i) { return (double)(splitmix64(seed, i) >> 11) * (1.0 / 9007199254740992.0); };
+  for (int64_t i = 0; i < nB; i++) {
+    dk[(size_t)i] = ((i * 7919) % nB) % nkeys;
+    dx[(size_t)i] = unit(0xD3, (uint64_t)i);
+  }
+  for (int64_t i = 0; i < n; i++) {
+    fk[(size_t)i] = (int64_t)(splitmix64(0xF1, (uint64_t)i) % (uint64_t)(nkeys + nkeys / 4));
+    fv[(size_t)i] = unit(0xF2, (uint64_t)i);
+  }
+  // the count the paths must reach, from the inputs alone: the build rows by key (counting sort), every probe row against its key's rows
+  int64_t expect = 0;
+  {
+    std::vector<int64_t> start((size_t)nkeys + 1, 0), rows((size_t)nB);
+    for (int64_t i = 0; i < nB; i++) start[(size_t)dk[(size_t)i] + 1]++;
+    for (int64_t k = 0; k < nkeys; k++) start[(size_t)k + 1] += start[(size_t)k];
+    std::vector<int64_t> at(start.begin(), start.end() - 1);
+    for (int64_t i = 0; i < nB; i++) rows[(size_t)at[(size_t)dk[(size_t)i]]++] = i;
+    std::vector<char> kept((size_t)nB, 0);
+    const bool outer_right = jt == SQLRS_JOIN_RIGHT || jt == SQLRS_JOIN_FULL, outer_left = jt == SQLRS_JOIN_LEFT || jt == SQLRS_JOIN_FULL;
+    for (int64_t i = 0; i < n; i++) {
+      int64_t pass = 0;
+      if (fk[(size_t)i] < nkeys)
+        for (int64_t q = start[(size_t)fk[(size_t)i]]; q < start[(size_t)fk[(size_t)i] + 1]; q++)
+          if (dx[(size_t)rows[(size_t)q]] > fv[(size_t)i]) {
+            pass++;
+            kept[(size_t)rows[(size_t)q]] = 1;
+          }
+      expect += outer_right ? std::max<int64_t>(pass, 1) : pass;
+    }
+    if (outer_left)
+      for (int64_t i = 0; i < nB; i++) expect += !kept[(size_t)i];
+  }
+  sqlrs_expr_node_t k0{};
+  k0.op = SQLRS_EXPR_INPUT_REF;
+  k0.index = 0;
+  sqlrs_expr_t key{&k0, 1, 0};
+  sqlrs_expr_node_t fn[3] = {}; // joined schema: l.k 0, l.x 1, r.k 2, r.v 3
+  fn[0].op = SQLRS_EXPR_INPUT_REF;
+  fn[0].index = 1;
+  fn[1].op = SQLRS_EXPR_INPUT_REF;
+  fn[1].index = 3;
+  fn[2].op = SQLRS_EXPR_GT;
+  sqlrs_expr_t filter{fn, 3, 0};
+  const int32_t right_dtypes[2] = {SQLRS_INT64, SQLRS_FLOAT64};
+  const int DEPTH = 8;
+  const int64_t nb = (n + B - 1) / B;
+  double best[3] = {1e30, 1e30, 1e30}; // push, push_async switch off, push_async switch on
+  int64_t joined[3] = {0, 0, 0};
+  bool ok = true;
+  auto run = [&](int path, int rep) -> int { // 0 ok
+    auto t0 = std::chrono::steady_clock::now();
+    sqlrs_hash_join_t *j = nullptr;
+    CHECK(sqlrs_hash_join_create(ctx, jt, 1, &key, &key, &filter, 2, right_dtypes, &j));
+    if (path) CHECK(sqlrs_hash_join_set_async_general(j, 1));
+#ifndef SQLRS_BENCH_NO_ASYNC_FILTER
+    if (path == 2) CHECK(sqlrs_hash_join_set_async_filter(j, 1));
+#endif
+    sqlrs_column_t lc[2];
+    host_col(lc[0], SQLRS_INT64, dk.data(), nB);
+    host_col(lc[1], SQLRS_FLOAT64, dx.data(), nB);
+    sqlrs_batch_t lb{};
+    lb.num_rows = nB;
+    lb.num_columns = 2;
+    lb.columns = lc;
+    CHECK(sqlrs_hash_join_build_push(j, &lb));
+    CHECK(sqlrs_hash_join_build_finish(j));
+    int64_t got = 0;
+    auto consume = [&](sqlrs_batch_t *o) { // a row with a build side passed the filter on equal keys
+      if (!o) return;
+      if (rep == 0 && o->num_rows) {
+        const int64_t *lk = (const int64_t *)o->columns[0].values, *rk = (const int64_t *)o->columns[2].values;
+        const double *lx = (const double *)o->columns[1].values, *rv = (const double *)o->columns[3].values;
+        const uint8_t *xv = (const uint8_t *)o->columns[1].validity;
+        for (int64_t r = 0; r < o->num_rows; r += 97) {
+          const bool matched = !xv || !o->columns[1].null_count || ((xv[r >> 3] >> (r & 7)) & 1);
+          ok = ok && (matched ? lk[r] == rk[r] && lx[r] > rv[r] : (jt == SQLRS_JOIN_RIGHT || jt == SQLRS_JOIN_FULL));
+        }
+      }
+      got += o->num_rows;
+      sqlrs_batch_release(o);
+    };
+    std::vector<sqlrs_ticket_t *> q((size_t)DEPTH, nullptr);
+    for (int64_t b = 0; b < nb + (path ? DEPTH : 0); b++) {
+      if (path && b >= DEPTH) {
+        sqlrs_batch_t *o = nullptr;
+        CHECK(sqlrs_batch_wait(q[(size_t)(b % DEPTH)], &o));
+        consume(o);
+      }
+      if (b >= nb) continue;
+      const int64_t lo = b * B, m = std::min<int64_t>(B, n - lo);
+      sqlrs_column_t rc[2];
+      host_col(rc[0], SQLRS_INT64, fk.data() + lo, m);
+      host_col(rc[1], SQLRS_FLOAT64, fv.data() + lo, m);
+      sqlrs_batch_t rb{};
+      rb.num_rows = m;
+      rb.num_columns = 2;
+      rb.columns = rc;
+      if (path) {
+        CHECK(sqlrs_hash_join_probe_push_async(j, &rb, &q[(size_t)(b % DEPTH)]));
+      } else {
+        sqlrs_batch_t *o = nullptr;
+        CHECK(sqlrs_hash_join_probe_push(j, &rb, SQLRS_MEM_HOST, &o));
+        consume(o);
+      }
+    }
+    sqlrs_batch_t *tail = nullptr;
+    CHECK(sqlrs_hash_join_finish(j, SQLRS_MEM_HOST, &tail));
+    if (tail) {
+      got += tail->num_rows;
+      sqlrs_batch_release(tail);
+    }
+    sqlrs_hash_join_destroy(j);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    joined[path] = got;
+    if (rep > 0 && ms < best[path]) best[path] = ms;
+    return 0;
+  };
+  for (int rep = 0; rep < 3; rep++)
+    if (run(0, rep)) return 1;
+  for (int rep = 0; rep < 3; rep++) // off and on alternate
+    for (int path = 1; path < npaths; path++)
+      if (run(path, rep)) return 1;
+  for (int path = 0; path < npaths; path++) ok = ok && joined[path] == expect;
+  std::printf("{\"mode\": \"probe_filter\", \"join\": \"%s\", \"dup\": %lld, \"probe_rows\": %lld, \"build_rows\": %lld, \"batch_rows\": %lld, "
+              "\"joined\": %lld, \"expected\": %lld, \"depth\": %d, \"ms_push\": %.1f, \"Mrows_s_push\": %.1f, \"ms_push_async_off\": %.1f, "
+              "\"Mrows_s_push_async_off\": %.1f, ",
+              jname, (long long)dup, (long long)n, (long long)nB, (long long)B, (long long)joined[0], (long long)expect, DEPTH, best[0],
+              (double)n / best[0] / 1e3, best[1], (double)n / best[1] / 1e3);
+  if (npaths == 3)
+    std::printf("\"ms_push_async_on\": %.1f, \"Mrows_s_push_async_on\": %.1f, \"on_over_off\": %.2f, ", best[2], (double)n / best[2] / 1e3, best[1] / best[2]);
+  std::printf("\"check\": \"%s\", \"note\": \"native caller (C ABI): build side one host batch (every key %lld times, a float64 payload), probe side "
+              "pageable %lld-row host batches (a fifth of the keys without partner, a float64 payload), join filter l.x > r.v (about half the pairs "
+              "pass), joined batches on the host; push = sqlrs_hash_join_probe_push per batch, push_async_off / _on = "
+              "sqlrs_hash_join_probe_push_async with sqlrs_hash_join_set_async_general 1 and sqlrs_hash_join_set_async_filter 0 / 1 (alternating "
+              "runs)%s; Mrows/s = probe rows; build included; best of 2 after a warm-up\"}\n",
+              ok ? "OK" : "mismatch", (long long)dup, (long long)B, npaths == 3 ? "" : "; built without the setter: no on path");
+  sqlrs_ctx_destroy(ctx);
+  return ok ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
+  if (argc > 1 && std::strcmp(argv[1], "probe_filter") == 0) return bench_probe_filter(argc, argv);
   if (argc > 1 && std::strcmp(argv[1], "probe_general") == 0) return bench_probe_general(argc, argv, false);
   if (argc > 1 && std::strcmp(argv[1], "probe_utf8") == 0) return bench_probe_general(argc, argv, true);
   if (argc > 1 && std::strcmp(argv[1], "filter") == 0) return bench_filter(argc, argv);

@@ -467,6 +467,7 @@ struct HashJoinExecutor { // hash_join.rs:16-23
   size_t depth = 0;        // probe batches through sqlrs_hash_join_probe_push_async, that many tickets in flight (see FilterExecutor)
   bool async_general = false; // sqlrs_hash_join_set_async_general: with depth > 0, outer joins and duplicate build keys in one launch per batch too
   bool async_utf8 = false;    // sqlrs_hash_join_set_async_utf8: with depth > 0, batches with Utf8 payload columns on either side in one launch too
+  bool async_filter = false;  // sqlrs_hash_join_set_async_filter: with depth > 0, a join with a join filter in one launch per batch too (the filter inside the kernel)
 
   BoxedExecutor execute() {
     struct S : Executor {
@@ -557,6 +558,7 @@ struct HashJoinExecutor { // hash_join.rs:16-23
                                       join_condition.filter ? &fe : nullptr, (int)right_dtypes.size(), right_dtypes.data(), &s->j));
     if (async_general) ctx->check(sqlrs_hash_join_set_async_general(s->j, 1));
     if (async_utf8) ctx->check(sqlrs_hash_join_set_async_utf8(s->j, 1));
+    if (async_filter) ctx->check(sqlrs_hash_join_set_async_filter(s->j, 1));
     return s;
   }
 };

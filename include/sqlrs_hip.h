@@ -381,6 +381,35 @@ int sqlrs_hash_join_set_async_general(sqlrs_hash_join_t *j, int on);
  * ever fail).  Everything else — the bound exceeded, Boolean columns, a Utf8 key, and the rest of the lists above — runs
  * the synchronous operator inside push_async, as with the switch off. */
 int sqlrs_hash_join_set_async_utf8(sqlrs_hash_join_t *j, int on);
+/* on != 0: both one-launch kernels of sqlrs_hash_join_probe_push_async also serve a join that HAS a join filter
+ * (JoinCondition::On { on, filter }): the filter is evaluated on the joined row inside the kernel, with
+ * apply_join_filter's semantics (hash_join.rs:47-127).  Default 0: exactly today's behaviour (a filtered join takes no
+ * fast batch).  Calling rules as for sqlrs_hash_join_set_async_general (after create, before the first probe call of any
+ * kind; later: SQLRS_ERR_INTERNAL; j == NULL: SQLRS_ERR_INTERNAL); the contract of probe_push_async is unchanged.  A join
+ * without a filter is not affected by the switch.
+ *
+ * Eligibility of a probe batch of a join that has a filter, with the switch on: every condition the batch would have to
+ * meet without the filter, except "no join filter" — the Inner / unique-build-keys fast path; or the general path when
+ * sqlrs_hash_join_set_async_general is on; with Utf8 payload columns when sqlrs_hash_join_set_async_utf8 is on — and the
+ * same OUTPUT BOUND with the same formulas, taken over the CANDIDATES, rows x M: the filter never makes a batch emit more
+ * rows than it has candidates (a Right / Full probe row emits max(passing pairs, 1) <= max(matches, 1) rows).  In
+ * addition the FILTER MUST COMPILE for the in-kernel evaluator, over the joined schema (the build side's columns, then
+ * the num_right_columns right_dtypes given to sqlrs_hash_join_create): at most 24 nodes, an evaluation stack of at most
+ * 8; every referenced column int32 / int64 / float64; constants int32 / int64 / float64 / Boolean (NULL allowed); casts
+ * between those types; both operands of an arithmetic or comparison node of one type; a Boolean result — the rule of
+ * sqlrs_filter_push_async's general predicates.  It is compiled once per join; a probe batch whose column dtypes are not
+ * right_dtypes is not eligible.  A filter that does not compile (it reads a Utf8 / Boolean column, is too long, mixes
+ * operand types) runs the synchronous operator inside push_async, as with the switch off.
+ *
+ * Semantics, bit for bit those of the synchronous operator.  Inner / Left: the candidates are the matched pairs (probe-row
+ * major, build insertion order minor); a pair is kept iff the filter is valid and TRUE on it (NULL drops it).  Right /
+ * Full: the candidates also hold one (NULL, r) row per probe row r without partner, the filter is evaluated on those too
+ * (every build column NULL); the batch is the kept candidates in candidate order, followed by one (NULL, r) row for every
+ * probe row that appears in no kept candidate, in ascending r.  Left / Full: only build rows of KEPT pairs count as
+ * visited for the tail batch of sqlrs_hash_join_finish.  A valid candidate row that divides by zero makes that ticket's
+ * sqlrs_batch_wait return SQLRS_ERR_ARROW "Divide by zero error"; the batch marks no build row visited, later tickets
+ * are unaffected. */
+int sqlrs_hash_join_set_async_filter(sqlrs_hash_join_t *j, int on);
 /* The index-pair form of one probe batch, before any gather: 2 columns
  * (UINT64 left index, nullable; UINT32 right index), in the reference's order
  * (probe-row major, build insertion order minor), join filter NOT applied.

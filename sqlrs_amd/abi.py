@@ -386,6 +386,7 @@ class Backend:
             "hash_join_probe_push_async": (i, [vp, pb, pvp]),
             "hash_join_set_async_general": (i, [vp, C.c_int]),
             "hash_join_set_async_utf8": (i, [vp, C.c_int]),
+            "hash_join_set_async_filter": (i, [vp, C.c_int]),
             "project_push_async": (i, [vp, pb, pvp]),
             "batch_wait": (i, [vp, ppb]),
             "batch_import_arrow": (i, [vp, C.POINTER(ArrowArrayC), C.POINTER(ArrowSchemaC), ppb]),

@@ -141,7 +141,13 @@ bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int f
 }
 
 bool sa_compile(const Expr &e, const sqlrs_batch_t *in, SaProgram *out) {
-  if (!in || e.nodes.empty() || e.nodes.size() > (size_t)SA_PROG_MAX) return false;
+  if (!in || in->num_columns < 0) return false;
+  std::vector<int32_t> dt((size_t)in->num_columns);
+  for (int c = 0; c < in->num_columns; c++) dt[(size_t)c] = in->columns[c].dtype;
+  return sa_compile(e, dt.data(), in->num_columns, out);
+}
+bool sa_compile(const Expr &e, const int32_t *dtypes, int ncols, SaProgram *out) {
+  if (e.nodes.empty() || e.nodes.size() > (size_t)SA_PROG_MAX) return false;
   int32_t st[SA_STACK_MAX];
   int sp = 0;
   out->n = 0;
@@ -151,8 +157,8 @@ bool sa_compile(const Expr &e, const sqlrs_batch_t *in, SaProgram *out) {
     SaInstr I{};
     switch (n.op) {
     case SQLRS_EXPR_INPUT_REF: {
-      if (n.index < 0 || n.index >= in->num_columns || sp >= SA_STACK_MAX) return false;
-      const int32_t d = in->columns[n.index].dtype;
+      if (n.index < 0 || n.index >= ncols || sp >= SA_STACK_MAX) return false;
+      const int32_t d = dtypes[n.index];
       if (!numeric(d)) return false; // (Boolean columns are bit-packed, Utf8 has no place on this stack)
       I.op = SAO_COL;
       I.dtype = (uint8_t)d;

@@ -1212,12 +1212,49 @@ struct SaProbeParams {
 struct SaProbeUtf8Params : SaProbeParams {
   const int32_t *loffs[SA_MAX_COLS]; // build columns: the offsets of a Utf8 column (lvals = its bytes) or null
 };
-template <bool UTF8>
-__global__ __launch_bounds__(1024) void sa_probe_kernel(SaGroup<std::conditional_t<UTF8, SaProbeUtf8Params, SaProbeParams>> grp) {
+// sqlrs_hash_join_set_async_filter (FILTER = true; joins without a filter keep the instantiations they always had): the join
+// filter as a postfix program over the JOINED row, compiled once per join (sa_probe_filter_ready) and read from HBM into LDS
+// at kernel start.  The operand loader of sa_eval_row for the joined row {build row, probe row}: a build column comes from HBM
+// (NULL when the row has no partner, else the column's 64-bit-word bitmap), a probe column from the slot.
+template <class Base> struct SaWithFilter : Base {
+  const SaProgram *prog; // HBM
+  SaWithFilter() = default;
+  SaWithFilter(const Base &b, const SaProgram *pr) : Base(b), prog(pr) {}
+};
+template <class P> struct SaJoinedLoad {
+  const P &p;
+  uint32_t r, brow;
+  __device__ __forceinline__ unsigned long long operator()(uint32_t c, bool *ok) const {
+    if ((int)c >= p.nleft) return SaSlotLoad{p.lay, p.in, r}(c, ok);
+    if (brow == DENSE_EMPTY) {
+      *ok = false;
+      return 0ull;
+    }
+    const uint64_t *lv = p.lvalid[c];
+    *ok = !lv || ((lv[brow >> 6] >> (brow & 63)) & 1);
+    return p.lay.c[c].width == 8 ? ((const unsigned long long *)p.lvals[c])[brow] : (unsigned long long)(long long)((const int32_t *)p.lvals[c])[brow];
+  }
+};
+// the program from HBM into LDS (every thread of the workgroup calls it; the caller's next barrier makes it readable)
+__device__ __forceinline__ void sa_load_program(const SaProgram *from, unsigned char *s_raw) {
+  static_assert(sizeof(SaProgram) % 4 == 0, "copied in words");
+  for (uint32_t i = threadIdx.x; i < (uint32_t)(sizeof(SaProgram) / 4); i += blockDim.x) ((uint32_t *)s_raw)[i] = ((const uint32_t *)from)[i];
+}
+template <bool UTF8, bool FILTER> using SaProbeP =
+    std::conditional_t<FILTER, SaWithFilter<std::conditional_t<UTF8, SaProbeUtf8Params, SaProbeParams>>, std::conditional_t<UTF8, SaProbeUtf8Params, SaProbeParams>>;
+template <bool UTF8, bool FILTER>
+__global__ __launch_bounds__(1024) void sa_probe_kernel(SaGroup<SaProbeP<UTF8, FILTER>> grp) {
   const auto &p = grp.p[blockIdx.x]; // (one workgroup per batch of the group)
   __shared__ uint32_t s_w[17], s_nulls[SA_MAX_COLS];
   __shared__ uint8_t s_v[SA_MAX_ROWS];
   if (threadIdx.x < SA_MAX_COLS) s_nulls[threadIdx.x] = 0;
+  [[maybe_unused]] __shared__ __attribute__((aligned(8))) unsigned char s_prog_raw[FILTER ? sizeof(SaProgram) : 8]; // (SaProgram has member initialisers)
+  [[maybe_unused]] __shared__ uint32_t s_div0;
+  if constexpr (FILTER) {
+    sa_load_program(p.prog, s_prog_raw);
+    if (threadIdx.x == 0) s_div0 = 0;
+    __syncthreads();
+  }
   const SaCol &kc = p.lay.c[p.nleft + p.key_col];
   uint32_t m[4] = {DENSE_EMPTY, DENSE_EMPTY, DENSE_EMPTY, DENSE_EMPTY}, pos[4], total;
   const uint32_t bits = sa_positions(
@@ -1231,6 +1268,14 @@ __global__ __launch_bounds__(1024) void sa_probe_kernel(SaGroup<std::conditional
         } else {
           const Slot sl = probe_slot(p.table, p.mask, key, false);
           if (sl.count) h = sl.head;
+        }
+        if constexpr (FILTER) {
+          if (h != DENSE_EMPTY) { // a candidate pair: kept iff the filter is valid and TRUE on the joined row (a NULL drops it)
+            bool valid, div0 = false;
+            const unsigned long long v = sa_eval_row(*(const SaProgram *)s_prog_raw, SaJoinedLoad<SaProbeP<UTF8, FILTER>>{p, r, h}, &valid, &div0);
+            if (div0) s_div0 = 1u;
+            if (!(valid && v != 0)) h = DENSE_EMPTY;
+          }
         }
         m[t] = h;
         return h != DENSE_EMPTY;
@@ -1318,18 +1363,24 @@ __global__ __launch_bounds__(1024) void sa_probe_kernel(SaGroup<std::conditional
     }
     if (lvalid || rvalid) sa_pack_validity(s_v, total, p.out + col.out_voff, &s_nulls[c]);
   }
-  if constexpr (UTF8) {
+  if constexpr (UTF8 && FILTER) { // (s_div0: every keep_of ran in front of sa_positions' barriers; 1 = the evaluator's error at the wait)
+    __shared__ uint32_t s_err;
+    if (threadIdx.x == 0) s_err = failed ? 2u : s_div0;
+    sa_publish((SaHeader *)p.out, p.seq, failed ? 0u : total, s_nulls, p.lay.ncols, &s_err);
+  } else if constexpr (FILTER) {
+    sa_publish((SaHeader *)p.out, p.seq, total, s_nulls, p.lay.ncols, &s_div0);
+  } else if constexpr (UTF8) {
     __shared__ uint32_t s_err;
     if (threadIdx.x == 0) s_err = failed ? 2u : 0u;
     sa_publish((SaHeader *)p.out, p.seq, failed ? 0u : total, s_nulls, p.lay.ncols, &s_err);
   } else
     sa_publish((SaHeader *)p.out, p.seq, total, s_nulls, p.lay.ncols);
 }
-template <bool UTF8> static void sa_probe_launch(SaRing *r, Ctx *ctx) {
-  using P = std::conditional_t<UTF8, SaProbeUtf8Params, SaProbeParams>;
+template <bool UTF8, bool FILTER = false> static void sa_probe_launch(SaRing *r, Ctx *ctx) {
+  using P = SaProbeP<UTF8, FILTER>;
   SaGroup<P> g;
   for (int i = 0; i < r->pend_n; i++) std::memcpy(&g.p[i], r->pend_buf + (size_t)i * SA_PARAM_MAX, sizeof(P));
-  sa_probe_kernel<UTF8><<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g);
+  sa_probe_kernel<UTF8, FILTER><<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g);
   SQ_HIP(hipGetLastError());
 }
 // Lmax of every Utf8 build column: the longest string in bytes, NULL slots included — what one output row can cost at the most
@@ -1386,14 +1437,52 @@ static void sa_probe_front_bytes(sqlrs_hash_join *j, uint64_t out_rows, uint64_t
   const std::vector<int64_t> &lmax = hash_join_utf8_lmax(j);
   for (size_t c = 0; c < lmax.size(); c++) front_bytes[c] = lmax[c] > 0 ? out_rows * (uint64_t)lmax[c] : 0;
 }
+// sqlrs_hash_join_set_async_filter: true = the join's filter runs inside the probe kernels for `right`.  The program is compiled
+// once per join over the joined schema — the build side's dtypes, then the right_dtypes of sqlrs_hash_join_create — with
+// sa_compile's rule (<= SA_PROG_MAX nodes, stack <= SA_STACK_MAX, int32 / int64 / float64 columns, Boolean result); a batch
+// whose dtypes are not right_dtypes keeps the synchronous operator
+static bool sa_probe_filter_ready(sqlrs_hash_join *j, const sqlrs_batch_t *right) {
+  if (!j->has_filter || !j->async_filter || !right) return false;
+  if (!j->filter_prog_state) {
+    std::vector<int32_t> dt;
+    for (const DCol &c : j->left.cols) dt.push_back(c.dtype);
+    dt.insert(dt.end(), j->right_dtypes.begin(), j->right_dtypes.end());
+    SaProgram prog;
+    const bool ok = !j->right_dtypes.empty() && sa_compile(j->filter, dt.data(), (int)dt.size(), &prog) && prog.result_dtype == SQLRS_BOOLEAN;
+    if (ok) {
+      j->filter_prog_host.assign(sizeof(SaProgram), 0);
+      std::memcpy(j->filter_prog_host.data(), &prog, sizeof(SaProgram));
+    }
+    j->filter_prog_state = ok ? 1 : -1;
+  }
+  if (j->filter_prog_state != 1 || (size_t)right->num_columns != j->right_dtypes.size()) return false;
+  for (int c = 0; c < right->num_columns; c++)
+    if (right->columns[c].dtype != j->right_dtypes[(size_t)c]) return false;
+  return true;
+}
+// the program in HBM (uploaded once, on the ctx stream) and, `pairs`: the general kernel's list regions, one per ring slot
+// (allocated once, from the ctx pool; freed with the join, whose destruction drains the side streams first).  Called before a
+// slot is taken (it may throw) and only by a join's fast batches, so the first batch that is enqueued — the one that orders the
+// side streams behind the ctx stream (async_ordered) — comes after the upload
+static void sa_probe_filter_device(sqlrs_hash_join *j, bool pairs) {
+  Ctx *ctx = j->ctx;
+  if (!j->filter_prog) {
+    BufP prog = ctx->alloc(sizeof(SaProgram));
+    SQ_HIP(hipMemcpyAsync(prog->p, j->filter_prog_host.data(), sizeof(SaProgram), hipMemcpyHostToDevice, ctx->stream));
+    j->filter_prog = prog;
+  }
+  if (pairs && !j->filter_pairs) j->filter_pairs = ctx->alloc((size_t)SA_SLOTS * SA_MAX_OUT_ROWS * sizeof(uint2));
+}
 // true = the kernel above was queued for `right` and *t describes its slot
 static bool sa_probe_try(sqlrs_hash_join *j, const sqlrs_batch_t *right, sqlrs_ticket *t) {
   Ctx *ctx = j->ctx;
   const char *off_e = hook("SQLRS_ASYNC_FAST"); // test hook, read per call: 0 = every batch through the synchronous operator
   if (off_e && off_e[0] == '0') return false;
-  if (j->join_type != SQLRS_JOIN_INNER || j->has_filter || !j->exact || j->comp.on || j->lkeys.size() != 1 || j->rkeys[0].nodes.size() != 1 ||
+  if (j->join_type != SQLRS_JOIN_INNER || !j->exact || j->comp.on || j->lkeys.size() != 1 || j->rkeys[0].nodes.size() != 1 ||
       j->rkeys[0].nodes[0].op != SQLRS_EXPR_INPUT_REF || !right)
     return false;
+  const bool filt = sa_probe_filter_ready(j, right);
+  if (j->has_filter && !filt) return false;
   const int kc = j->rkeys[0].nodes[0].index;
   if (kc < 0 || kc >= right->num_columns) return false;
   const sqlrs_column_t &kcol = right->columns[kc];
@@ -1410,6 +1499,7 @@ static bool sa_probe_try(sqlrs_hash_join *j, const sqlrs_batch_t *right, sqlrs_t
   if (!j->unique || (!j->dense && !j->table)) return false;
   uint64_t front_bytes[SA_MAX_COLS] = {};
   if (utf8 && right->num_rows >= 0 && right->num_rows <= (int64_t)SA_MAX_ROWS) sa_probe_front_bytes(j, (uint64_t)right->num_rows, front_bytes);
+  if (filt) sa_probe_filter_device(j, false); // (may throw: before a slot is taken)
   SaRing *r = sa_ring(ctx);
   const int slot = r ? sa_take_slot(r) : -1;
   if (slot < 0) return false;
@@ -1433,11 +1523,14 @@ static bool sa_probe_try(sqlrs_hash_join *j, const sqlrs_batch_t *right, sqlrs_t
   p.in = r->in_area(slot);
   p.out = r->out_area(slot);
   p.seq = ++r->seq;
-  if (!j->async_ordered) { // the table and the build columns were queued on the ctx stream: the side streams wait for them, once
+  if (!j->async_ordered) { // the table and the build columns (and the filter's program) were queued on the ctx stream: the side streams wait for them, once
     sa_order_after_ctx(ctx, r);
     j->async_ordered = true;
   }
-  if (utf8) sa_enqueue(ctx, r, j, sa_probe_launch<true>, p, slot);
+  const SaProgram *prog = filt ? j->filter_prog->as<SaProgram>() : nullptr;
+  if (filt && utf8) sa_enqueue(ctx, r, j, sa_probe_launch<true, true>, SaWithFilter<SaProbeUtf8Params>(p, prog), slot);
+  else if (filt) sa_enqueue(ctx, r, j, sa_probe_launch<false, true>, SaWithFilter<SaProbeParams>(p, prog), slot);
+  else if (utf8) sa_enqueue(ctx, r, j, sa_probe_launch<true>, p, slot);
   else sa_enqueue(ctx, r, j, sa_probe_launch<false>, (const SaProbeParams &)p, slot);
   t->slot = slot;
   t->seq = p.seq;
@@ -1483,18 +1576,43 @@ struct SaProbeGenParams {
 struct SaProbeGenUtf8Params : SaProbeGenParams {
   const int32_t *loffs[SA_MAX_COLS]; // build columns: the offsets of a Utf8 column (lvals = its bytes) or null
 };
-template <bool UTF8>
-__global__ __launch_bounds__(1024) void sa_probe_general_kernel(SaGroup<std::conditional_t<UTF8, SaProbeGenUtf8Params, SaProbeGenParams>> grp) {
+// sqlrs_hash_join_set_async_filter (FILTER = true; joins without a filter keep the instantiations they always had) — the join
+// filter with apply_join_filter's semantics (hash_join.rs:47-127), two phases inside the one launch.  Phase A walks the
+// CANDIDATES — the rows the kernel would emit without a filter, Right / Full: a (NULL, r) row per probe row without partner
+// included — one thread each, evaluates the program on the joined row and compacts the kept ones stably (ballot + mbcnt + a
+// running base across the 1024-candidate chunks) into a list of {probe row, build row | DENSE_EMPTY} in HBM (`pairs`: a region
+// per ring slot; 16384 x 8 bytes do not fit LDS next to s_off / s_start), setting a bit per probe row that kept a candidate
+// (s_kept, LDS); Right / Full: the probe rows whose bit stayed clear are appended as {r, DENSE_EMPTY}, ascending.  Phase B is
+// the emit loop over the list instead of the search.  A workgroup's writes of phase A are ordered before its reads of phase B
+// by the barrier between them.  `visited` is marked in phase B only: by kept pairs, and not at all when a valid candidate
+// divided by zero (the batch's wait raises the evaluator's error, SaHeader::pad = 1).
+template <class Base> struct SaGenWithFilter : Base {
+  const SaProgram *prog; // HBM
+  uint2 *pairs;          // HBM: room for `cap` entries
+  SaGenWithFilter() = default;
+  SaGenWithFilter(const Base &b, const SaProgram *pr, uint2 *pl) : Base(b), prog(pr), pairs(pl) {}
+};
+template <bool UTF8, bool FILTER> using SaProbeGenP =
+    std::conditional_t<FILTER, SaGenWithFilter<std::conditional_t<UTF8, SaProbeGenUtf8Params, SaProbeGenParams>>, std::conditional_t<UTF8, SaProbeGenUtf8Params, SaProbeGenParams>>;
+template <bool UTF8, bool FILTER>
+__global__ __launch_bounds__(1024) void sa_probe_general_kernel(SaGroup<SaProbeGenP<UTF8, FILTER>> grp) {
   const auto &p = grp.p[blockIdx.x]; // (one workgroup per batch of the group)
   __shared__ uint32_t s_off[SA_MAX_ROWS], s_start[SA_MAX_ROWS]; // per probe row: first output row; run start / build row / DENSE_EMPTY
   __shared__ uint32_t s_w[16], s_nulls[SA_MAX_COLS], s_err;
   [[maybe_unused]] __shared__ uint32_t s_ubase[SA_MAX_COLS]; // Utf8: bytes of the column emitted by the chunks so far
+  [[maybe_unused]] __shared__ __attribute__((aligned(8))) unsigned char s_prog_raw[FILTER ? sizeof(SaProgram) : 8]; // (SaProgram has member initialisers)
+  [[maybe_unused]] __shared__ uint32_t s_kept[FILTER ? SA_MAX_ROWS / 32 : 1], s_div0; // FILTER: bit r = probe row r has a kept candidate
   [[maybe_unused]] bool failed = false;
   const int lane = lane_id(), w = wave_id();
   if (threadIdx.x < SA_MAX_COLS) s_nulls[threadIdx.x] = 0;
   if constexpr (UTF8)
     if (threadIdx.x < SA_MAX_COLS) s_ubase[threadIdx.x] = 0;
   if (threadIdx.x == 0) s_err = 0;
+  if constexpr (FILTER) { // (the lookup loop below has barriers: all of this is in place before phase A)
+    sa_load_program(p.prog, s_prog_raw);
+    if (threadIdx.x < SA_MAX_ROWS / 32) s_kept[threadIdx.x] = 0;
+    if (threadIdx.x == 0) s_div0 = 0;
+  }
   const uint32_t rows = p.lay.rows;
   const SaCol &kc = p.lay.c[p.nleft + p.key_col];
   uint32_t base = 0;
@@ -1543,20 +1661,89 @@ __global__ __launch_bounds__(1024) void sa_probe_general_kernel(SaGroup<std::con
     total = 0;
     if (threadIdx.x == 0) s_err = 2;
   }
+  if constexpr (FILTER) {
+    __syncthreads(); // (rows = 0: the loop above had no barrier)
+    const SaProgram &prog = *(const SaProgram *)s_prog_raw;
+    uint32_t kbase = 0; // entries of the list so far
+    for (uint32_t o0 = 0; o0 < total; o0 += 1024u) { // phase A (uniform): candidate o of the batch
+      const uint32_t o = o0 + threadIdx.x;
+      uint32_t r = 0, brow = DENSE_EMPTY;
+      bool keep = false;
+      if (o < total) {
+        uint32_t lo = 0, hi = rows; // the last probe row whose first candidate is <= o (s_off[0] = 0)
+        while (hi - lo > 1) {
+          const uint32_t mid = (lo + hi) >> 1;
+          if (s_off[mid] <= o) lo = mid;
+          else hi = mid;
+        }
+        r = lo;
+        const uint32_t st = s_start[r];
+        if (st != DENSE_EMPTY) brow = p.unique ? st : p.rows_by_slot[st + (o - s_off[r])];
+        bool valid, div0 = false;
+        const unsigned long long v = sa_eval_row(prog, SaJoinedLoad<SaProbeGenP<UTF8, FILTER>>{p, r, brow}, &valid, &div0);
+        if (div0) s_div0 = 1u;
+        keep = valid && v != 0;
+      }
+      const uint64_t bm = __ballot(keep);
+      if (lane == 0) s_w[w] = (uint32_t)__popcll(bm);
+      __syncthreads();
+      uint32_t before = 0, all = 0;
+#pragma unroll
+      for (int q = 0; q < 16; q++) {
+        const uint32_t c = s_w[q];
+        before += q < w ? c : 0;
+        all += c;
+      }
+      if (keep) { // (kbase + all <= o0 + 1024, at most `total` <= cap: inside the slot's region)
+        p.pairs[kbase + before + mbcnt(bm)] = make_uint2(r, brow);
+        atomicOr(&s_kept[r >> 5], 1u << (r & 31));
+      }
+      kbase += all;
+      __syncthreads();
+    }
+    if (p.outer_right) // the probe rows that kept no candidate come back as (NULL, r) behind the kept ones, in row order (:73-121)
+      for (uint32_t t = 0; t * 1024u < rows; t++) { // (uniform)
+        const uint32_t r = t * 1024u + threadIdx.x;
+        const bool lost = total && r < rows && !((s_kept[r >> 5] >> (r & 31)) & 1); // (total = 0 with rows > 0: the slot was too small, nothing is written)
+        const uint64_t bm = __ballot(lost);
+        if (lane == 0) s_w[w] = (uint32_t)__popcll(bm);
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+#pragma unroll
+        for (int q = 0; q < 16; q++) {
+          const uint32_t c = s_w[q];
+          before += q < w ? c : 0;
+          all += c;
+        }
+        if (lost) p.pairs[kbase + before + mbcnt(bm)] = make_uint2(r, DENSE_EMPTY); // (a row that lost all <= one candidate each: the list stays <= total)
+        kbase += all;
+        __syncthreads();
+      }
+    total = s_div0 ? 0u : kbase; // (uniform: every write of s_div0 and of the list has a barrier behind it) a division by zero emits and marks nothing
+  }
   for (uint32_t o0 = 0; o0 < total; o0 += 1024u) { // (uniform)
     const uint32_t o = o0 + threadIdx.x;
     const bool act = o < total;
     uint32_t r = 0, brow = DENSE_EMPTY;
-    if (act) {
-      uint32_t lo = 0, hi = rows; // the last probe row whose first output row is <= o (s_off[0] = 0)
-      while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (s_off[mid] <= o) lo = mid;
-        else hi = mid;
+    if constexpr (FILTER) {
+      if (act) {
+        const uint2 pr = p.pairs[o];
+        r = pr.x;
+        brow = pr.y;
       }
-      r = lo;
-      const uint32_t st = s_start[r];
-      if (st != DENSE_EMPTY) brow = p.unique ? st : p.rows_by_slot[st + (o - s_off[r])];
+    }
+    if (act) {
+      if constexpr (!FILTER) {
+        uint32_t lo = 0, hi = rows; // the last probe row whose first output row is <= o (s_off[0] = 0)
+        while (hi - lo > 1) {
+          const uint32_t mid = (lo + hi) >> 1;
+          if (s_off[mid] <= o) lo = mid;
+          else hi = mid;
+        }
+        r = lo;
+        const uint32_t st = s_start[r];
+        if (st != DENSE_EMPTY) brow = p.unique ? st : p.rows_by_slot[st + (o - s_off[r])];
+      }
       if (p.mark && brow != DENSE_EMPTY) { // (bits only ever get set: a plain read decides whether the atomic is needed, mark_bits_kernel)
         const unsigned long long bit = 1ull << (brow & 63);
         if (!(__hip_atomic_load(&p.visited[brow >> 6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) atomicOr(&p.visited[brow >> 6], bit);
@@ -1640,13 +1827,15 @@ __global__ __launch_bounds__(1024) void sa_probe_general_kernel(SaGroup<std::con
       for (int c = 0; c < p.lay.ncols; c++)
         if (p.lay.c[c].dtype == SQLRS_UTF8) ((int32_t *)(p.out + p.lay.c[c].out_off))[total] = (int32_t)(failed ? 0u : s_ubase[c]);
   }
+  if constexpr (FILTER)
+    if (threadIdx.x == 0 && s_div0 && !s_err) s_err = 1; // (thread 0 reads both behind phase A's last barrier; sa_publish reads s_err behind its own)
   sa_publish((SaHeader *)p.out, p.seq, total, s_nulls, p.lay.ncols, &s_err);
 }
-template <bool UTF8> static void sa_probe_general_launch(SaRing *r, Ctx *ctx) {
-  using P = std::conditional_t<UTF8, SaProbeGenUtf8Params, SaProbeGenParams>;
+template <bool UTF8, bool FILTER = false> static void sa_probe_general_launch(SaRing *r, Ctx *ctx) {
+  using P = SaProbeGenP<UTF8, FILTER>;
   SaGroup<P> g;
   for (int i = 0; i < r->pend_n; i++) std::memcpy(&g.p[i], r->pend_buf + (size_t)i * SA_PARAM_MAX, sizeof(P));
-  sa_probe_general_kernel<UTF8><<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g);
+  sa_probe_general_kernel<UTF8, FILTER><<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g);
   SQ_HIP(hipGetLastError());
 }
 // M: the most build rows that share one key — the largest Slot.count of the 16-byte-slot table (its NULL-key slot included) or
@@ -1680,9 +1869,11 @@ static bool sa_probe_general_try(sqlrs_hash_join *j, const sqlrs_batch_t *right,
   if (!j->async_general) return false;
   const char *off_e = hook("SQLRS_ASYNC_FAST"); // test hook, read per call: 0 = every batch through the synchronous operator
   if (off_e && off_e[0] == '0') return false;
-  if (j->has_filter || !j->exact || j->comp.on || j->lkeys.size() != 1 || j->rkeys[0].nodes.size() != 1 ||
+  if (!j->exact || j->comp.on || j->lkeys.size() != 1 || j->rkeys[0].nodes.size() != 1 ||
       j->rkeys[0].nodes[0].op != SQLRS_EXPR_INPUT_REF || !right || right->num_rows < 0 || right->num_rows > (int64_t)SA_MAX_ROWS)
     return false;
+  const bool filt = sa_probe_filter_ready(j, right);
+  if (j->has_filter && !filt) return false;
   const int kc = j->rkeys[0].nodes[0].index;
   if (kc < 0 || kc >= right->num_columns) return false;
   const sqlrs_column_t &kcol = right->columns[kc];
@@ -1704,6 +1895,7 @@ static bool sa_probe_general_try(sqlrs_hash_join *j, const sqlrs_batch_t *right,
   if (out_rows > SA_MAX_OUT_ROWS) return false;
   uint64_t front_bytes[SA_MAX_COLS] = {};
   if (utf8) sa_probe_front_bytes(j, out_rows, front_bytes);
+  if (filt) sa_probe_filter_device(j, true); // (may throw: before a slot is taken)
   SaRing *r = sa_ring(ctx);
   const int slot = r ? sa_take_slot(r) : -1;
   if (slot < 0) return false;
@@ -1736,11 +1928,15 @@ static bool sa_probe_general_try(sqlrs_hash_join *j, const sqlrs_batch_t *right,
   p.in = r->in_area(slot);
   p.out = r->out_area(slot);
   p.seq = ++r->seq;
-  if (!j->async_ordered) { // the table, the build columns and the cleared `visited` were queued on the ctx stream: the side streams wait for them, once
+  if (!j->async_ordered) { // the table, the build columns and the cleared `visited` (and the filter's program) were queued on the ctx stream: the side streams wait for them, once
     sa_order_after_ctx(ctx, r);
     j->async_ordered = true;
   }
-  if (utf8) sa_enqueue(ctx, r, j, sa_probe_general_launch<true>, p, slot);
+  const SaProgram *prog = filt ? j->filter_prog->as<SaProgram>() : nullptr;
+  uint2 *pairs = filt ? j->filter_pairs->as<uint2>() + (size_t)slot * SA_MAX_OUT_ROWS : nullptr; // (a slot is reused only after its ticket was waited for)
+  if (filt && utf8) sa_enqueue(ctx, r, j, sa_probe_general_launch<true, true>, SaGenWithFilter<SaProbeGenUtf8Params>(p, prog, pairs), slot);
+  else if (filt) sa_enqueue(ctx, r, j, sa_probe_general_launch<false, true>, SaGenWithFilter<SaProbeGenParams>(p, prog, pairs), slot);
+  else if (utf8) sa_enqueue(ctx, r, j, sa_probe_general_launch<true>, p, slot);
   else sa_enqueue(ctx, r, j, sa_probe_general_launch<false>, (const SaProbeGenParams &)p, slot);
   t->slot = slot;
   t->seq = p.seq;
@@ -1777,6 +1973,14 @@ int sqlrs_hash_join_set_async_general(sqlrs_hash_join_t *j, int on) {
   return guard(j->ctx, [&] {
     if (j->probe_started) fail(SQLRS_ERR_INTERNAL, "sqlrs_hash_join_set_async_general: after the first probe call");
     j->async_general = on != 0;
+  });
+}
+// the switch of the join filter inside both async probe kernels: before the first probe call of any kind
+int sqlrs_hash_join_set_async_filter(sqlrs_hash_join_t *j, int on) {
+  if (!j) return SQLRS_ERR_INTERNAL;
+  return guard(j->ctx, [&] {
+    if (j->probe_started) fail(SQLRS_ERR_INTERNAL, "sqlrs_hash_join_set_async_filter: after the first probe call");
+    j->async_filter = on != 0;
   });
 }
 // the switch of the Utf8 payload columns in both async probe kernels: before the first probe call of any kind

@@ -96,6 +96,15 @@ struct sqlrs_hash_join {
   // build column c in bytes, NULL slots included (-1: not a Utf8 column), computed when the first batch needs it (utf8_lmax_known)
   bool async_utf8 = false, utf8_lmax_known = false;
   std::vector<int64_t> utf8_lmax;
+  // sqlrs_hash_join_set_async_filter: both async probe kernels evaluate the join filter on the joined row (sa_eval_row, join.hip).
+  // The filter is compiled ONCE per join, over the build side's dtypes followed by `right_dtypes` (filter_prog_state: 0 not tried
+  // yet, 1 compiled, -1 not expressible — such a join keeps the synchronous operator), and uploaded once (filter_prog: one
+  // SaProgram in HBM, filter_prog_host the bytes it was copied from).  filter_pairs: the general kernel's list of kept
+  // {probe row, build row} pairs, SA_MAX_OUT_ROWS x 8 bytes per ring slot, allocated when the first batch needs it
+  bool async_filter = false;
+  int filter_prog_state = 0;
+  std::vector<unsigned char> filter_prog_host;
+  sq::BufP filter_prog, filter_pairs;
 };
 
 // builds the deferred hash table of a `lazy_table` join (join.hip); no-op otherwise

@@ -13,7 +13,7 @@
 //   * `wait` polls the header's sequence number (system-scope release store behind `__threadfence_system`), falling
 //     back to a stream synchronisation when it does not show up, and copies the rows into an ordinary HOST batch.
 // Anything the fast path does not take — predicates that read a Boolean / Utf8 column or need more than 24 nodes, Utf8
-// columns around a join (unless the join's Utf8 switch is on, last paragraph), more than 4096 rows, DEVICE input, join filters, NULL probe keys, composite or hash-only join keys,
+// columns around a join (unless the join's Utf8 switch is on, below), more than 4096 rows, DEVICE input, join filters (unless the join's filter switch is on, last paragraph), NULL probe keys, composite or hash-only join keys,
 // duplicate build keys and outer joins (unless the join's switch is on, next paragraph) — runs the synchronous operator
 // inside push_async and parks the finished batch in the ticket: same results, same one-output-per-input rule, no speed-up.
 // sqlrs_hash_join_set_async_general(j, 1): Left / Right / Full joins and build sides with duplicate keys take ONE launch per
@@ -26,6 +26,13 @@
 // column.  The host reserves out_rows x Lmax bytes for a build column (Lmax: its longest string, NULL slots included, one kernel
 // and one fetch per join) and B x (out_rows / rows) for a probe column of B bytes, and admits the batch only when that fits the
 // slot; the kernels check every column's bytes against SaCol::out_cap before they store one.
+// sqlrs_hash_join_set_async_filter(j, 1): both probe kernels also serve a join WITH a join filter (FILTER = true instantiations):
+// the filter is compiled once per join into an SaProgram over the joined schema (sa_compile over a dtype list), uploaded once,
+// copied into LDS at kernel start and evaluated by sa_eval_row through a joined-row operand loader (build columns from HBM,
+// probe columns from the slot).  sa_probe_kernel keeps a matched row iff the filter is valid and TRUE; sa_probe_general_kernel
+// evaluates it per candidate, compacts the kept candidates into a list in HBM (a region per ring slot), appends the Right / Full
+// probe rows that kept none, and emits from the list — apply_join_filter's order and its visited marks; a valid candidate that
+// divides by zero is SaHeader::pad = 1, the evaluator's error at the wait.  The output bound is the unfiltered one (candidates).
 #pragma once
 
 #include <cstring>
@@ -145,6 +152,8 @@ struct SaProgram {
 // Expr -> program over the columns of `in`; false = not expressible here (a Utf8 / Boolean column or constant, mixed operand
 // types, an unsupported cast, too long): the synchronous evaluator takes the batch and raises whatever error there is to raise
 bool sa_compile(const Expr &e, const sqlrs_batch_t *in, SaProgram *out);
+// the same over a list of column dtypes (a join's filter: the build side's columns, then the probe side's)
+bool sa_compile(const Expr &e, const int32_t *dtypes, int ncols, SaProgram *out);
 
 } // namespace sq
 
@@ -160,18 +169,30 @@ struct sqlrs_ticket {
 #if defined(__HIPCC__)
 #include "device_utils.hpp"
 namespace sq {
-// one row of the program: *valid = the result is not NULL; *div0 raised when a valid row divides by zero
-__device__ __forceinline__ unsigned long long sa_eval_row(const SaProgram &pr, const SaLayout &lay, const uint8_t *in, uint32_t r, bool *valid,
-                                                          bool *div0) {
+// the operand loader of a batch in its slot: column `c` of row `r` (int32 sign-extended), *ok = the value is not NULL
+struct SaSlotLoad {
+  const SaLayout &lay;
+  const uint8_t *in;
+  uint32_t r;
+  __device__ __forceinline__ unsigned long long operator()(uint32_t col, bool *ok) const {
+    const SaCol &c = lay.c[col];
+    *ok = c.in_voff == SA_NONE || ((in[c.in_voff + (r >> 3)] >> (r & 7)) & 1);
+    return c.width == 8 ? ((const unsigned long long *)(in + c.in_off))[r] : (unsigned long long)(long long)((const int32_t *)(in + c.in_off))[r];
+  }
+};
+// one row of the program: *valid = the result is not NULL; *div0 raised when a valid row divides by zero.  `load(column, &ok)`
+// fetches an operand: SaSlotLoad for the Filter / Project kernels, the joined-row loader of the probe kernels (join.hip)
+template <class Load>
+__device__ __forceinline__ unsigned long long sa_eval_row(const SaProgram &pr, const Load &load, bool *valid, bool *div0) {
   unsigned long long v[SA_STACK_MAX];
   bool ok[SA_STACK_MAX];
   int sp = 0;
   for (int k = 0; k < pr.n; k++) {
     const SaInstr I = pr.ins[k];
     if (I.op == SAO_COL) {
-      const SaCol &c = lay.c[I.col];
-      ok[sp] = c.in_voff == SA_NONE || ((in[c.in_voff + (r >> 3)] >> (r & 7)) & 1);
-      v[sp] = c.width == 8 ? ((const unsigned long long *)(in + c.in_off))[r] : (unsigned long long)(long long)((const int32_t *)(in + c.in_off))[r];
+      bool o;
+      v[sp] = load(I.col, &o);
+      ok[sp] = o;
       sp++;
     } else if (I.op == SAO_CONST) {
       ok[sp] = !I.is_null;
@@ -256,6 +277,10 @@ __device__ __forceinline__ unsigned long long sa_eval_row(const SaProgram &pr, c
   }
   *valid = ok[0];
   return v[0];
+}
+__device__ __forceinline__ unsigned long long sa_eval_row(const SaProgram &pr, const SaLayout &lay, const uint8_t *in, uint32_t r, bool *valid,
+                                                          bool *div0) {
+  return sa_eval_row(pr, SaSlotLoad{lay, in, r}, valid, div0);
 }
 
 // Output positions of the kept rows of <= 4096 rows on ONE 1024-thread workgroup: pos[t] for row t * 1024 + tid, bit t of

@@ -141,7 +141,7 @@ class HashJoinExecutor:
     def __init__(self, backend: abi.Backend, left_child: Iterable, right_child: Iterable,
                  join_type: str, join_condition: JoinCondition, join_output_schema: pa.Schema,
                  num_left_columns: int, out_mem: int = abi.MEM_HOST, many: int = 0, depth: int = 0,
-                 async_general: bool = False, async_utf8: bool = False):
+                 async_general: bool = False, async_utf8: bool = False, async_filter: bool = False):
         self.backend = backend
         self.depth = depth  # > 0: probe batches through sqlrs_hash_join_probe_push_async, that many tickets in flight
         # sqlrs_hash_join_set_async_general: with depth > 0, outer joins and duplicate build keys take one launch per batch too
@@ -150,6 +150,9 @@ class HashJoinExecutor:
         # sqlrs_hash_join_set_async_utf8: with depth > 0, batches with Utf8 payload columns on either side take the one-launch
         # kernels too (again: a backend without the entry point runs unchanged)
         self.async_utf8 = async_utf8
+        # sqlrs_hash_join_set_async_filter: with depth > 0, a join WITH a join filter takes the one-launch kernels too, the filter
+        # evaluated inside them (again: a backend without the entry point runs unchanged)
+        self.async_filter = async_filter
         # many > 1: that many probe batches go to sqlrs_hash_join_probe_push_many together (same stream of joined batches)
         self.many = many
         self.left_child, self.right_child = left_child, right_child
@@ -175,7 +178,8 @@ class HashJoinExecutor:
         be.check(be.fn("hash_join_create")(
             be.ctx, JoinType[self.join_type.lower()], len(self.join_condition.on), lk, rk, filt,
             len(right_fields), rd, C.byref(h)))
-        for flag, name in ((self.async_general, "hash_join_set_async_general"), (self.async_utf8, "hash_join_set_async_utf8")):
+        for flag, name in ((self.async_general, "hash_join_set_async_general"), (self.async_utf8, "hash_join_set_async_utf8"),
+                           (self.async_filter, "hash_join_set_async_filter")):
             setter = getattr(be.lib, be.prefix + name, None)
             if flag and setter is not None:
                 st = setter(h, 1)
