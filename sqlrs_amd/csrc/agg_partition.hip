@@ -1669,6 +1669,14 @@ bool partitioned_preaggregate(Ctx *ctx, const PartAggSpec &spec, const PartAggIn
   out->gacc = ctx->alloc(8 * (size_t)gcap * (size_t)std::max(spec.n_acc, 1));
   out->gcap = gcap;
   if (!out->ov_rows) out->ov_rows = ctx->alloc(4 * (size_t)std::max<int64_t>(n, 1)); // (n: rows that passed the fused filter)
+  // (route witnesses: the form of this bucket pass, common.hpp Ctx::AggRoute; the kernel family is counted at its launch)
+  ctx->agg_route[pr.pack.kbits ? Ctx::AR_PACKED : Ctx::AR_UNPACKED]++;
+  ctx->agg_route[Ctx::AR_FLAGS] += pf != nullptr;
+  ctx->agg_route[Ctx::AR_REC] += pr.rec != nullptr;
+  ctx->agg_route[Ctx::AR_IN_PLACE] += in_place;
+  ctx->agg_route[Ctx::AR_JOIN] += join_mode;
+  ctx->agg_route[Ctx::AR_JOIN_MULT] += prm.partner_mult != nullptr;
+  ctx->agg_route[Ctx::AR_SPLIT] += nsplit > 0;
   {
     ProfScope ps(ctx, "lds_agg");
 #define SQ_LA(NV, FL, JN, NA, C0, C1, PK)                                                                        \
@@ -1686,6 +1694,7 @@ bool partitioned_preaggregate(Ctx *ctx, const PartAggSpec &spec, const PartAggIn
         ctr->as<unsigned long long>() + 1, out->ov_rows->as<uint32_t>(),                                       \
         bp ? bp->key->as<uint64_t>() : nullptr, (bp && bp->flags) ? bp->flags->as<uint8_t>() : nullptr,        \
         bp ? bp->bstart->as<uint32_t>() : nullptr, pr.pack, stb);                                              \
+    ctx->agg_route[NA < 0 ? Ctx::AR_PROBE_GENERIC : Ctx::AR_PROBE_SPEC]++;                                     \
     launched = true;                                                                                           \
   } while (0)
 #define SQ_LA_J(NV, FL, NA, C0, C1)                                                                            \
@@ -1723,6 +1732,8 @@ bool partitioned_preaggregate(Ctx *ctx, const PartAggSpec &spec, const PartAggIn
     kfn<<<dim3(nwork), dim3(DENSE_WG), slds, ctx->stream>>>(prm, sb, dwork->as<uint32_t>(), ctr->as<unsigned long long>(), \
                                                            out->gkey->as<uint64_t>(), out->gfirst->as<uint32_t>(), \
                                                            out->gacc->as<uint64_t>(), gcap, pr.pack, stb);        \
+    ctx->agg_route[blk ? Ctx::AR_SLIM_BLK : Ctx::AR_SLIM_RUNS]++;                                              \
+    ctx->agg_route[Ctx::AR_INTERPRETED] += NA < 0;                                                             \
     launched = true;                                                                                           \
   } while (0)
 #define SQ_LS_J(NA, C0, C1) do { if (join_mode) SQ_LS(true, NA, C0, C1); else SQ_LS(false, NA, C0, C1); } while (0)
@@ -1749,6 +1760,8 @@ bool partitioned_preaggregate(Ctx *ctx, const PartAggSpec &spec, const PartAggIn
         prm, pr.rec ? pr.rec->as<uint64_t>() : pk->as<uint64_t>(), pv0 ? pv0->as<uint64_t>() : nullptr, dwork->as<uint32_t>(), \
         ctr->as<unsigned long long>(), out->gkey->as<uint64_t>(), out->gfirst->as<uint32_t>(),                 \
         out->gacc->as<uint64_t>(), gcap, pr.pack, stb);                                                        \
+    ctx->agg_route[Ctx::AR_DENSE]++;                                                                           \
+    ctx->agg_route[Ctx::AR_INTERPRETED] += NA < 0;                                                             \
     launched = true;                                                                                           \
   } while (0)
 #define SQ_LD_J(NV, NA, C0, C1) do { if (join_mode) SQ_LD(NV, true, NA, C0, C1); else SQ_LD(NV, false, NA, C0, C1); } while (0)
@@ -1809,6 +1822,7 @@ bool partitioned_preaggregate(Ctx *ctx, const PartAggSpec &spec, const PartAggIn
   }
   out->groups = (int64_t)h[0];
   out->n_overflow = (int64_t)h[1];
+  ctx->agg_route[Ctx::AR_OVERFLOW_ROWS] += out->n_overflow;
   out->may_dup = h[3] != 0; // a split bucket's global table was full: some keys were emitted twice
   if (join_mode && h[2]) return false; // a bucket table could not hold its build keys
   if (out->groups > gcap) return false; // estimate far too low: caller falls back to the resolve path

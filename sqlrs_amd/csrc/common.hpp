@@ -157,6 +157,27 @@ struct Ctx {
   int lb_backoff = 0; // resident blocks per CU of the persistent kernels, per kernel
   int64_t async_conj_batches = 0;   // ... of them, Filter batches whose predicate took the conjunction kernel form, not the program (profile: "async_conj_batches")
   int64_t async_fast_batches = 0;   // batches the single-batch async path took with its one-launch kernels (profile: "async_fast_batches")
+  // Which form of the aggregate routes ran (counts, reported by sqlrs_ctx_profile_read under the names in AGG_ROUTE_NAMES
+  // when non-zero; incremented on the host where the launch is chosen — DESIGN.md "Route witnesses of the aggregates").
+  // One bucket pass of partitioned_preaggregate moves exactly one of DENSE / SLIM_RUNS / SLIM_BLK / PROBE_SPEC /
+  // PROBE_GENERIC and exactly one of PACKED / UNPACKED.
+  enum AggRoute {
+    AR_DENSE, AR_SLIM_RUNS, AR_SLIM_BLK, AR_PROBE_SPEC, AR_PROBE_GENERIC, // kernel family of the bucket pass
+    AR_INTERPRETED,  // a dense / slim pass whose accumulator list is interpreted per row (no specialised signature)
+    AR_PACKED, AR_UNPACKED, // (key, row) packed into one word, or key and row id columns
+    AR_FLAGS,        // rows carry per-row validity flags (a nullable key or value column)
+    AR_REC,          // 16-byte {word, value} records instead of columns
+    AR_IN_PLACE,     // one bucket: the caller's columns read in place, no partition pass
+    AR_JOIN,         // fused join: build keys decide which rows count
+    AR_JOIN_MULT,    // ... with duplicate build keys: cells multiplied by the key's build rows
+    AR_SPLIT,        // the pass cut at least one bucket into chunks (split tables merged by an emit kernel)
+    AR_OVERFLOW_ROWS, // rows that found no slot and went back through the row route
+    AR_MERGE_GROUPS, // hashagg_op: pre-aggregated groups merged into the table state with weights
+    AR_PENDING,      // hashagg_op: a pre-aggregated batch deferred as the operator's whole state
+    AR_WIDE_PARTS,   // hashagg_op: partition-route operators a wide aggregate list was run as (per pushed batch)
+    AR_COUNT_
+  };
+  int64_t agg_route[AR_COUNT_] = {};
   std::shared_ptr<void> small_ring; // the pinned ring of the single-batch async path (small_async.hpp), created on first use
   void sync() { SQ_HIP(hipStreamSynchronize(stream)); }
   // copies `bytes` from device to the pinned area and synchronises; returns host pointer

@@ -298,6 +298,7 @@ static void update_from_rows(sqlrs_hash_agg *a, const BufP &rgbuf, const std::ve
 // cells accumulate with weights (O(groups) global atomics)
 static void merge_groups(sqlrs_hash_agg *a, PendingGroups &pg) {
   Ctx *ctx = a->ctx;
+  ctx->agg_route[Ctx::AR_MERGE_GROUPS]++;
   PartAggOutput &po = pg.po;
   NKeys gk;
   gk.rows = po.groups;
@@ -642,9 +643,10 @@ static bool agg_consume(sqlrs_hash_agg *a, int64_t n, const std::vector<DCol> &k
               pg.keyvals.push_back(gather_column(ctx, kc, po.gfirst->p, false, nullptr, po.groups));
           }
           pg.po = po;
-          if (a->st.ngroups == 0 && po.n_overflow == 0 && !po.may_dup)
+          if (a->st.ngroups == 0 && po.n_overflow == 0 && !po.may_dup) {
             a->pending = std::move(pg); // nothing to merge with yet: defer building the table
-          else
+            ctx->agg_route[Ctx::AR_PENDING]++;
+          } else
             merge_groups(a, pg);
           // rows whose bucket table was full go through the row route
           if (po.n_overflow) {
@@ -970,6 +972,7 @@ static int hash_agg_push_parts(sqlrs_hash_agg_t *a, const sqlrs_batch_t *in0) {
     if (st != SQLRS_OK) return st;
     in = dev;
   }
+  a->ctx->agg_route[Ctx::AR_WIDE_PARTS] += (int64_t)a->parts.size();
   for (sqlrs_hash_agg *p : a->parts) {
     st = hash_agg_push_device(p, in, filtered);
     if (st != SQLRS_OK) {
