@@ -178,6 +178,26 @@ struct Ctx {
     AR_COUNT_
   };
   int64_t agg_route[AR_COUNT_] = {};
+  // Which form of the hash join's routes ran (counts, reported like agg_route under JOIN_ROUTE_NAMES, ctx.hip, behind the
+  // aggregates' entries; incremented on the host where the launch is chosen — DESIGN.md "Route witnesses of the join").
+  // One direct-address attempt moves exactly one of ONE_FETCH / TWO_FETCH, one of PACKED / PLAIN when a table was filled,
+  // and — once its verdict is read — one of ADOPTED / REFUSED.
+  enum JoinRoute {
+    JR_DENSE_ADOPTED,  // the direct-address table became the join's table (unique keys over an admissible range)
+    JR_DENSE_REFUSED,  // attempted and not adopted: the range refused (dense_range.hpp), or duplicate keys
+    JR_DENSE_ONE_FETCH, JR_DENSE_TWO_FETCH, // the build sized for the largest admissible range, or from the range it fetched
+    JR_DENSE_PACKED, JR_DENSE_PLAIN, // a bit-packed copy for the probe kernels beside the 4-byte table, or the 4-byte table alone
+    JR_PROBE_PENDING,  // a first probe that ran on the device-side verdict (dense_pending)
+    JR_ALLHIT_KEPT, JR_ALLHIT_REDONE, // an optimistic all-hit probe whose pairs stood, or that saw a miss / a refused build
+    JR_COMPACT_DENSE, JR_COMPACT_SLOTS, // the compacting probe of the direct-address table, or of the 16-byte-slot table
+    JR_UNIQUE_OUTER,   // join_probe_unique_outer_kernel (Right / Full over unique build keys)
+    JR_DD_STREAM, JR_DD_ROWS, // dd_count_stream_kernel, or dd_count_kernel
+    JR_COUNTS_GROUPED, JR_COUNTS_PER_ROW, // pair counts per 64-row group, or per row
+    JR_LDS_UNIQUE, JR_LDS_DISTINCT, // a batch matched on LDS tables of the build keys, or of its distinct keys
+    JR_TABLE_LATE,     // the general table built by hash_join_ensure_table, not by the build
+    JR_COUNT_
+  };
+  int64_t join_route[JR_COUNT_] = {};
   std::shared_ptr<void> small_ring; // the pinned ring of the single-batch async path (small_async.hpp), created on first use
   void sync() { SQ_HIP(hipStreamSynchronize(stream)); }
   // copies `bytes` from device to the pinned area and synchronises; returns host pointer

@@ -1274,6 +1274,21 @@ int sqlrs_ctx_profile_read(sqlrs_ctx_t *ctx, int cap, const char **names, double
     }
     n++;
   }
+  // (counts: which form of the hash join's routes ran — common.hpp: Ctx::JoinRoute, in that order; behind every older entry)
+  static const char *const JOIN_ROUTE_NAMES[Ctx::JR_COUNT_] = {
+      "join_dense_adopted", "join_dense_refused", "join_dense_one_fetch", "join_dense_two_fetch", "join_dense_packed",
+      "join_dense_plain", "join_probe_pending", "join_allhit_kept", "join_allhit_redone", "join_compact_dense",
+      "join_compact_slots", "join_unique_outer", "join_dd_stream", "join_dd_rows", "join_counts_grouped",
+      "join_counts_per_row", "join_lds_unique", "join_lds_distinct", "join_table_late"};
+  for (int r = 0; r < Ctx::JR_COUNT_; r++) {
+    if (!ctx->join_route[r]) continue;
+    if (n < cap) {
+      names[n] = JOIN_ROUTE_NAMES[r];
+      total_ms[n] = 0;
+      launches[n] = ctx->join_route[r];
+    }
+    n++;
+  }
   return n;
 }
 

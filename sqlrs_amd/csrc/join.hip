@@ -230,10 +230,12 @@ static void dense_resolve(sqlrs_hash_join *j, const uint64_t *h = nullptr) {
   for (int i = 0; i < DENSE_MM; i++) nlo = std::max(nlo, hw[i]), hi = std::max(hi, hw[DENSE_MM + i]);
   const uint64_t lo = ~nlo, occupied = hw[2 * DENSE_MM], nulls = hw[2 * DENSE_MM + 1];
   const uint32_t null_head = (uint32_t)hw[2 * DENSE_MM + 2];
-  const uint64_t range = hi - lo + 1;
-  if (lo <= hi && range <= j->pend_max_range && range < (1ull << 31)) { // (what dense_dev decided)
+  const DenseRange dr = dense_range_decide(lo, hi, j->pend_max_range); // (what dense_dev decided)
+  const uint64_t range = dr.range;
+  if (dr.ok) {
     const uint64_t dmin = lo ^ (1ull << 63);
     if (nulls <= 1 && occupied + nulls == (uint64_t)n) {
+      ctx->join_route[Ctx::JR_DENSE_ADOPTED]++;
       j->unique = true;
       j->unique_known = j->table_built = true;
       j->dense = dense;
@@ -253,6 +255,7 @@ static void dense_resolve(sqlrs_hash_join *j, const uint64_t *h = nullptr) {
       j->dup_range = range;
     }
   }
+  ctx->join_route[Ctx::JR_DENSE_REFUSED]++;
   if (j->lazy_table) return; // built by hash_join_ensure_table when something probes it
   if (build_dense_dup(j)) return; // duplicate keys over a dense range: runs by key, no general table
   if (lds_build_first(j)) return; // general keys on LDS tables: uniqueness from there, the global table on first need only
@@ -356,6 +359,8 @@ static void build_table(sqlrs_hash_join *j) {
       dense_count_dev_kernel<<<dim3(cblocks), dim3(256), 0, ctx->stream>>>(dense->as<uint32_t>(), stp, max_range, stp + 2 * DENSE_MM);
     }
     SQ_HIP(hipGetLastError());
+    ctx->join_route[Ctx::JR_DENSE_ONE_FETCH]++;
+    ctx->join_route[bits ? Ctx::JR_DENSE_PACKED : Ctx::JR_DENSE_PLAIN]++;
     j->dense_pending = true;
     j->pend_st = st;
     j->pend_dense = dense;
@@ -381,14 +386,18 @@ static void build_table(sqlrs_hash_join *j) {
     SQ_HIP(hipGetLastError());
     const uint64_t *h = (const uint64_t *)ctx->fetch(mm->p, 16);
     uint64_t lo = h[0], hi = h[1];
+    ctx->join_route[Ctx::JR_DENSE_TWO_FETCH]++;
+    ctx->join_route[Ctx::JR_DENSE_REFUSED]++; // (taken back where the table is adopted)
     if (lo <= hi) {
-      uint64_t range = hi - lo + 1; // ordered images differ like the signed values
+      // ordered images differ like the signed values
       // (a join owned by a HashJoin+HashAgg takes the table up to 16 slots per key: its fused route then partitions
       //  by key range and needs only the existence bitmap of the range — a filtered dimension, or the hash-partitioned
       //  shard of one that a rank of the multi-GPU plan receives, 1/8 of the keys of the range for 8 ranks)
       const char *pj_e = hook("SQLRS_DENSE_JOIN_SLOTS_PLAIN"); // tuning hook, read per call
       const uint64_t slots_per_key = j->lazy_table ? DENSE_SLOTS_PER_KEY_OWNED : (pj_e ? (uint64_t)std::max(1, std::atoi(pj_e)) : 4);
-      if (range <= slots_per_key * (uint64_t)n + 1024 && range < (1ull << 31)) {
+      const DenseRange dr = dense_range_decide(lo, hi, slots_per_key * (uint64_t)n + 1024);
+      const uint64_t range = dr.range;
+      if (dr.ok) {
         ProfScope ps(ctx, "join_build_dense");
         BufP dense = ctx->alloc(4 * (size_t)range + 8);
         SQ_HIP(hipMemsetAsync(dense->p, 0xff, 4 * (size_t)range + 8, ctx->stream));
@@ -404,7 +413,10 @@ static void build_table(sqlrs_hash_join *j) {
         SQ_HIP(hipGetLastError());
         const uint64_t *hc = (const uint64_t *)ctx->fetch(cnt->p, 24); // one round trip for all three
         const uint32_t hd[2] = {(hc[1] <= 1 && hc[0] + hc[1] == (uint64_t)n) ? 0u : 1u, (uint32_t)hc[2]};
+        ctx->join_route[Ctx::JR_DENSE_PLAIN]++;
         if (hd[0] == 0) {
+          ctx->join_route[Ctx::JR_DENSE_REFUSED]--;
+          ctx->join_route[Ctx::JR_DENSE_ADOPTED]++;
           j->unique = true;
           j->unique_known = j->table_built = true;
           j->dense = dense;
@@ -633,7 +645,10 @@ static void build_hash_table(sqlrs_hash_join *j) {
 
 void hash_join_ensure_table(sqlrs_hash_join *j) {
   dense_resolve(j);
-  if (!j->table_built && j->finished && !j->empty_build && !build_dense_dup(j)) build_hash_table(j);
+  if (!j->table_built && j->finished && !j->empty_build && !build_dense_dup(j)) {
+    j->ctx->join_route[Ctx::JR_TABLE_LATE]++;
+    build_hash_table(j);
+  }
 }
 
 static DenseTable dense_table_of(const sqlrs_hash_join *j) {
@@ -686,9 +701,11 @@ static Pairs probe_pairs(sqlrs_hash_join *j, const NKeys &pk) {
         join_probe_dense_allhit_packed_kernel<false><<<dim3(pblocks), dim3(256), 0, ctx->stream>>>(pk.keys->as<uint64_t>(), n, dt, p.left->as<uint64_t>(),
                                                                                                 p.right->as<uint32_t>(), miss);
       SQ_HIP(hipGetLastError());
+      ctx->join_route[Ctx::JR_PROBE_PENDING]++;
       uint64_t hw[DENSE_ST_WORDS + 1];
       std::memcpy(hw, ctx->fetch(j->pend_st->p, 8 * (DENSE_ST_WORDS + 1)), sizeof(hw));
       dense_resolve(j, hw);
+      ctx->join_route[(j->dense && (unsigned int)hw[DENSE_ST_WORDS] == 0) ? Ctx::JR_ALLHIT_KEPT : Ctx::JR_ALLHIT_REDONE]++;
       if (j->dense && (unsigned int)hw[DENSE_ST_WORDS] == 0) { // a unique dense key set and every probe row found its partner
         p.m = n;
         p.right_identity = true;
@@ -745,7 +762,9 @@ static Pairs probe_pairs(sqlrs_hash_join *j, const NKeys &pk) {
           join_probe_dense_allhit_kernel<<<dim3(blocks), dim3(256), 0, ctx->stream>>>(pk.keys->as<uint64_t>(), n, dt, p.left->as<uint64_t>(),
                                                                                            p.right->as<uint32_t>(), miss);
         SQ_HIP(hipGetLastError());
-        if (ctx->fetch_value(miss) == 0) { // every pair is in place
+        const bool all_hit = ctx->fetch_value(miss) == 0;
+        ctx->join_route[all_hit ? Ctx::JR_ALLHIT_KEPT : Ctx::JR_ALLHIT_REDONE]++;
+        if (all_hit) { // every pair is in place
           p.m = n;
           p.right_identity = true;
           return p;
@@ -756,6 +775,7 @@ static Pairs probe_pairs(sqlrs_hash_join *j, const NKeys &pk) {
     BufP desc = ctx->alloc_zero(8 * (size_t)tiles + 24);
     unsigned *ticket = (unsigned *)(desc->as<uint64_t>() + tiles);
     uint64_t *tot = desc->as<uint64_t>() + tiles + 1;
+    if (!lm.ok) ctx->join_route[j->dense ? Ctx::JR_COMPACT_DENSE : Ctx::JR_COMPACT_SLOTS]++;
     for (int use_ticket = lookback_start_mode(ctx), attempt = 0; use_ticket < 2; use_ticket++, attempt++) {
       if (attempt) SQ_HIP(hipMemsetAsync(desc->p, 0, 8 * (size_t)tiles + 16, ctx->stream)); // rerun after a timeout
       {
@@ -798,6 +818,7 @@ static Pairs probe_pairs(sqlrs_hash_join *j, const NKeys &pk) {
     p.right = ctx->alloc(4 * (size_t)n);
     p.left_validity = ctx->alloc(bitmap_bytes(n));
     ProfScope ps(ctx, "join_probe_unique");
+    ctx->join_route[Ctx::JR_UNIQUE_OUTER]++;
     int64_t n64 = (int64_t)round_up((size_t)n, 64);
     DenseTable dt = dense_table_of(j);
     if (j->dense)
@@ -816,6 +837,7 @@ static Pairs probe_pairs(sqlrs_hash_join *j, const NKeys &pk) {
   // side of >= 2^26 rows — 64 runs of that length overflow a 32-bit sum — keeps per-row counts.
   const char *gr_e = hook("SQLRS_JOIN_GROUPED"); // test hook, read per call: 0 = per-row counts whatever the build side's size
   const int grouped = (j->nB < (1ll << 26) && !(gr_e && std::atoi(gr_e) == 0)) ? 1 : 0;
+  ctx->join_route[grouped ? Ctx::JR_COUNTS_GROUPED : Ctx::JR_COUNTS_PER_ROW]++;
   const int64_t nscan = grouped ? ceil_div(n, 64) : n;
   BufP counts = ctx->alloc(4 * (size_t)nscan), offsets = ctx->alloc(8 * (size_t)nscan), total = ctx->alloc(8);
   BufP match = ctx->alloc(8 * (size_t)n);
@@ -824,7 +846,9 @@ static Pairs probe_pairs(sqlrs_hash_join *j, const NKeys &pk) {
     lds_join_unpermute(j, lmg, n, outer_right, match->as<uint2>(), counts->as<uint32_t>(), grouped);
   } else if (j->dd_table) { // duplicate keys over a dense range: {run, rows} by direct address
     ProfScope ps(ctx, "join_probe_count_dense_dup");
-    if (!pk.validity && n >= JAP_ROWS && ((uintptr_t)pk.keys->p & 15) == 0) {
+    const bool stream = !pk.validity && n >= JAP_ROWS && ((uintptr_t)pk.keys->p & 15) == 0;
+    ctx->join_route[stream ? Ctx::JR_DD_STREAM : Ctx::JR_DD_ROWS]++;
+    if (stream) {
       const unsigned pblocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n / JAP_ROWS, 4), JAP_GRID * (int64_t)ctx->num_cus));
       dd_count_stream_kernel<<<dim3(pblocks), dim3(256), 0, ctx->stream>>>(pk.keys->as<uint64_t>(), n, j->dup_min, j->dup_range, j->dd_table->as<uint32_t>(),
                                                                          outer_right, counts->as<uint32_t>(), match->as<uint2>(), grouped);

@@ -563,6 +563,7 @@ LdsJoinMatch lds_join_match(sqlrs_hash_join *j, const NKeys &pk, bool distinct) 
         pbstart->as<uint32_t>(), nrs, (uint32_t)n, P, nranges, rpi, lds_slots, out.mpart->as<uint32_t>());
     SQ_HIP(hipGetLastError());
   }
+  ctx->join_route[distinct ? Ctx::JR_LDS_DISTINCT : Ctx::JR_LDS_UNIQUE]++;
   out.ok = true;
   return out;
 }

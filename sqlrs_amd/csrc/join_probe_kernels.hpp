@@ -7,6 +7,7 @@
 #include "device_utils.hpp"
 #include "prims.hpp"
 #include "join_kernels.hpp"
+#include "dense_range.hpp"
 
 namespace sq {
 
@@ -708,9 +709,10 @@ __device__ __forceinline__ DenseDev dense_dev(const unsigned long long *__restri
     hi = st[DENSE_MM + i] > hi ? st[DENSE_MM + i] : hi;
   }
   const uint64_t lo = ~nlo;
+  const DenseRange dr = dense_range_decide(lo, hi, max_range);
   DenseDev d;
-  d.range = hi - lo + 1;
-  d.ok = lo <= hi && d.range <= max_range && d.range < (1ull << 31);
+  d.range = dr.range;
+  d.ok = dr.ok;
   d.kmin = lo ^ (1ull << 63);
   return d;
 }
