@@ -96,7 +96,9 @@ impl HipFilterManyExecutor {
 /// The same operator polled ONE batch at a time, as the reference's loop reads, through `sqlrs_filter_push_async`: `depth`
 /// tickets in flight, the batch of the input read `depth` polls ago handed out by `sqlrs_batch_wait` — no stream
 /// synchronisation per batch and no regrouping of the child's stream (22 -> 168 Mrows/s at 1024-row batches).
-pub struct HipFilterAsyncExecutor { pub ctx: Arc<HipCtx>, pub expr: BoundExpr, pub child: BoxedExecutor, pub depth: usize }
+/// `async_all_types` (sqlrs_filter_set_async_all_types): predicates that read Utf8 / Boolean columns and batches that carry
+/// Boolean columns take the one-launch kernel too — the CSV tables' `WHERE state = 'CA'`; never a different batch.
+pub struct HipFilterAsyncExecutor { pub ctx: Arc<HipCtx>, pub expr: BoundExpr, pub child: BoxedExecutor, pub depth: usize, pub async_all_types: bool }
 impl HipFilterAsyncExecutor {
     #[try_stream(boxed, ok = RecordBatch, error = ExecutorError)]
     pub async fn execute(self) {
@@ -104,6 +106,7 @@ impl HipFilterAsyncExecutor {
         let mut f = std::ptr::null_mut();
         self.ctx.check(unsafe { sqlrs_filter_create(self.ctx.raw(), &expr.abi(), &mut f) })?;
         let _g = Guard(f, sqlrs_filter_destroy);
+        if self.async_all_types { self.ctx.check(unsafe { sqlrs_filter_set_async_all_types(f, 1) })?; }
         let mut inflight = Tickets(std::collections::VecDeque::new());
         let mut child = self.child;
         let mut ended = false;
@@ -315,7 +318,8 @@ impl HipProjectManyExecutor {
 }
 /// ... and polled ONE batch at a time through `sqlrs_project_push_async` with `depth` tickets in flight (see
 /// HipFilterAsyncExecutor; 11 -> 250 Mrows/s at 1024-row batches from the native caller).
-pub struct HipProjectAsyncExecutor { pub ctx: Arc<HipCtx>, pub exprs: Vec<BoundExpr>, pub child: BoxedExecutor, pub depth: usize }
+/// `async_all_types` (sqlrs_project_set_async_all_types): computed columns that read Utf8 / Boolean columns too.
+pub struct HipProjectAsyncExecutor { pub ctx: Arc<HipCtx>, pub exprs: Vec<BoundExpr>, pub child: BoxedExecutor, pub depth: usize, pub async_all_types: bool }
 impl HipProjectAsyncExecutor {
     #[try_stream(boxed, ok = RecordBatch, error = ExecutorError)]
     pub async fn execute(self) {
@@ -323,6 +327,7 @@ impl HipProjectAsyncExecutor {
         let mut p = std::ptr::null_mut();
         self.ctx.check(unsafe { sqlrs_project_create(self.ctx.raw(), ex.len() as i32, ex.as_ptr(), &mut p) })?;
         let _g = Guard(p, sqlrs_project_destroy);
+        if self.async_all_types { self.ctx.check(unsafe { sqlrs_project_set_async_all_types(p, 1) })?; }
         let mut inflight = Tickets(std::collections::VecDeque::new());
         let mut child = self.child;
         let mut ended = false;

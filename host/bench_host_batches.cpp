@@ -5,6 +5,7 @@
 //   ./bench_host_batches [rows = 2e7] [groups = 1e6] [batch = 1024]
 //   ./bench_host_batches filter ... | probe ...   the streaming operators at the same batch shape (see bench_filter / bench_probe)
 //   ./bench_host_batches probe_general ...         outer joins / duplicate build keys through push_async (see bench_probe_general)
+//   ./bench_host_batches filter_all_types ...      Utf8 / Boolean predicates through push_async (see bench_filter_all_types)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -777,7 +778,138 @@ static int bench_probe_filter(int argc, char **argv) {
   return ok ? 0 : 1;
 }
 
+// ./bench_host_batches filter_all_types [rows = 2e6] [batch = 1024]
+// FilterExecutor over the shape of the reference's CSV tables — {int64 k, float64 v, Utf8 s of 4-16 bytes, Boolean p} in pageable
+// 1024-row HOST batches (every batch's offsets a window into one array, so offsets[0] != 0; its bitmap a window of whole bytes) —
+// under `s = <constant> AND v > c` and `p AND v > c`: sqlrs_filter_push per batch, sqlrs_filter_push_async with
+// sqlrs_filter_set_async_all_types off (the synchronous operator inside push_async: what these predicates always took) and on
+// (one launch per batch, the operands read inside the kernel).  The three paths alternate; best of 2 after a warm-up; one JSON
+// line per predicate, `on_over_off` = ms off / ms on.
+static int bench_filter_all_types(int argc, char **argv) {
+  const int64_t n = argc > 2 ? (int64_t)std::atof(argv[2]) : 2000000;
+  const int64_t B = ((argc > 3 ? std::atoll(argv[3]) : 1024) + 7) / 8 * 8; // (whole bytes of bitmap per batch)
+  sqlrs_ctx_t *ctx = nullptr;
+  if (sqlrs_ctx_create(0, &ctx) != SQLRS_OK) {
+    std::printf("{\"error\": \"no device\"}\n");
+    return 2;
+  }
+  static const char *NAMES[16] = {"utah", "texas", "oregon", "alabama", "new york", "minnesota", "california", "mississippi",
+                                  "pennsylvania", "massachusetts", "north carolina", "west virginia x", "district of col.", "ohio", "idaho", "nevada"};
+  const char *WANT = "california";
+  const double c = 0.5;
+  std::vector<int64_t> k((size_t)n);
+  std::vector<double> v((size_t)n);
+  std::vector<int32_t> offs((size_t)n + 1);
+  std::vector<char> data;
+  std::vector<uint8_t> pbits((size_t)(n + 7) / 8 + 8, 0);
+  int64_t expect[2] = {0, 0};
+  offs[0] = 0;
+  for (int64_t i = 0; i < n; i++) {
+    k[(size_t)i] = (int64_t)(splitmix64(0xA7, (uint64_t)i) % 1000);
+    v[(size_t)i] = (double)(splitmix64(0xF2, (uint64_t)i) >> 11) * (1.0 / 9007199254740992.0);
+    const char *name = NAMES[splitmix64(0x57, (uint64_t)i) % 16];
+    data.insert(data.end(), name, name + std::strlen(name));
+    offs[(size_t)i + 1] = (int32_t)data.size();
+    const bool p = splitmix64(0xB0, (uint64_t)i) & 1;
+    if (p) pbits[(size_t)(i >> 3)] |= (uint8_t)(1u << (i & 7));
+    expect[0] += std::strcmp(name, WANT) == 0 && v[(size_t)i] > c;
+    expect[1] += p && v[(size_t)i] > c;
+  }
+  sqlrs_expr_node_t utf8_pred[7] = {}, bool_pred[5] = {};
+  utf8_pred[0].op = SQLRS_EXPR_INPUT_REF;
+  utf8_pred[0].index = 2;
+  utf8_pred[1].op = SQLRS_EXPR_CONSTANT;
+  utf8_pred[1].dtype = SQLRS_UTF8;
+  utf8_pred[1].s = WANT;
+  utf8_pred[2].op = SQLRS_EXPR_EQ;
+  utf8_pred[3].op = SQLRS_EXPR_INPUT_REF;
+  utf8_pred[3].index = 1;
+  utf8_pred[4].op = SQLRS_EXPR_CONSTANT;
+  utf8_pred[4].dtype = SQLRS_FLOAT64;
+  utf8_pred[4].f = c;
+  utf8_pred[5].op = SQLRS_EXPR_GT;
+  utf8_pred[6].op = SQLRS_EXPR_AND;
+  bool_pred[0].op = SQLRS_EXPR_INPUT_REF;
+  bool_pred[0].index = 3;
+  bool_pred[1] = utf8_pred[3];
+  bool_pred[2] = utf8_pred[4];
+  bool_pred[3] = utf8_pred[5];
+  bool_pred[4].op = SQLRS_EXPR_AND;
+  const sqlrs_expr_t preds[2] = {{utf8_pred, 7, 0}, {bool_pred, 5, 0}};
+  const char *pred_names[2] = {"s = 'california' AND v > 0.5", "p AND v > 0.5"};
+  const int64_t nb = (n + B - 1) / B;
+  std::vector<sqlrs_column_t> cols((size_t)nb * 4);
+  std::vector<sqlrs_batch_t> batches((size_t)nb);
+  for (int64_t b = 0; b < nb; b++) {
+    const int64_t m = std::min<int64_t>(B, n - b * B);
+    sqlrs_column_t *cc = &cols[(size_t)b * 4];
+    host_col(cc[0], SQLRS_INT64, k.data() + b * B, m);
+    host_col(cc[1], SQLRS_FLOAT64, v.data() + b * B, m);
+    host_col(cc[2], SQLRS_UTF8, data.data(), m);
+    cc[2].offsets = offs.data() + b * B;
+    host_col(cc[3], SQLRS_BOOLEAN, pbits.data() + b * B / 8, m);
+    std::memset(&batches[(size_t)b], 0, sizeof(sqlrs_batch_t));
+    batches[(size_t)b].num_rows = m;
+    batches[(size_t)b].num_columns = 4;
+    batches[(size_t)b].columns = cc;
+  }
+  const int DEPTH = 8; // tickets in flight, as in the other legs
+  bool all_ok = true;
+  for (int q = 0; q < 2; q++) {
+    double best[3] = {1e30, 1e30, 1e30};
+    int64_t kept[3] = {0, 0, 0};
+    for (int rep = 0; rep < 3; rep++) { // (the first repetition warms the pool and the ring; the paths alternate)
+      for (int path = 0; path < 3; path++) { // 0: push, 1: push_async with the switch off, 2: with it on
+        auto t0 = std::chrono::steady_clock::now();
+        sqlrs_filter_t *f = nullptr;
+        CHECK(sqlrs_filter_create(ctx, &preds[q], &f));
+        if (path == 2) CHECK(sqlrs_filter_set_async_all_types(f, 1));
+        int64_t got = 0;
+        if (path == 0) {
+          for (int64_t b = 0; b < nb; b++) {
+            sqlrs_batch_t *o = nullptr;
+            CHECK(sqlrs_filter_push(f, &batches[(size_t)b], SQLRS_MEM_HOST, &o));
+            got += o->num_rows;
+            sqlrs_batch_release(o);
+          }
+        } else {
+          std::vector<sqlrs_ticket_t *> tq((size_t)DEPTH, nullptr);
+          auto take = [&](int64_t b) {
+            sqlrs_batch_t *o = nullptr;
+            CHECK(sqlrs_batch_wait(tq[(size_t)(b % DEPTH)], &o));
+            got += o->num_rows;
+            sqlrs_batch_release(o);
+            return 0;
+          };
+          for (int64_t b = 0; b < nb; b++) {
+            if (b >= DEPTH && take(b - DEPTH)) return 1;
+            CHECK(sqlrs_filter_push_async(f, &batches[(size_t)b], &tq[(size_t)(b % DEPTH)]));
+          }
+          for (int64_t b = std::max<int64_t>(0, nb - DEPTH); b < nb; b++)
+            if (take(b)) return 1;
+        }
+        sqlrs_filter_destroy(f);
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        kept[path] = got;
+        if (rep > 0 && ms < best[path]) best[path] = ms;
+      }
+    }
+    const bool ok = kept[0] == expect[q] && kept[1] == expect[q] && kept[2] == expect[q];
+    all_ok = all_ok && ok;
+    std::printf("{\"leg\": \"filter_all_types\", \"predicate\": \"%s\", \"rows\": %lld, \"batches\": %lld, \"batch_rows\": %lld, \"kept\": %lld, "
+                "\"depth\": %d, \"ms_push\": %.1f, \"Mrows_s_push\": %.1f, \"ms_async_off\": %.1f, \"Mrows_s_async_off\": %.1f, "
+                "\"ms_async_on\": %.1f, \"Mrows_s_async_on\": %.1f, \"on_over_off\": %.2f, \"check\": \"%s\", \"note\": \"native caller (C ABI): "
+                "pageable %lld-row host batches {int64, float64, utf8 of 4-16 bytes, boolean}, one result batch per input batch on the host; "
+                "sqlrs_filter_push, then sqlrs_filter_push_async with sqlrs_filter_set_async_all_types 0 / 1 (alternating), best of 2 after a warm-up\"}\n",
+                pred_names[q], (long long)n, (long long)nb, (long long)B, (long long)kept[2], DEPTH, best[0], (double)n / best[0] / 1e3, best[1],
+                (double)n / best[1] / 1e3, best[2], (double)n / best[2] / 1e3, best[1] / best[2], ok ? "OK" : "mismatch", (long long)B);
+  }
+  sqlrs_ctx_destroy(ctx);
+  return all_ok ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
+  if (argc > 1 && std::strcmp(argv[1], "filter_all_types") == 0) return bench_filter_all_types(argc, argv);
   if (argc > 1 && std::strcmp(argv[1], "probe_filter") == 0) return bench_probe_filter(argc, argv);
   if (argc > 1 && std::strcmp(argv[1], "probe_general") == 0) return bench_probe_general(argc, argv, false);
   if (argc > 1 && std::strcmp(argv[1], "probe_utf8") == 0) return bench_probe_general(argc, argv, true);

@@ -392,6 +392,7 @@ struct FilterExecutor { // filter.rs:7-10
   // `depth` tickets in flight — next() hands out the batch of the input it read `depth` polls ago (sqlrs_batch_wait), so the
   // caller never waits for the device: 22 -> 168 Mrows/s at 1024-row batches, without regrouping the child's stream
   size_t depth = 0;
+  bool async_all_types = false; // sqlrs_filter_set_async_all_types: with depth > 0, predicates over Utf8 / Boolean columns and batches with Boolean columns in one launch too
   BoxedExecutor execute() {
     struct S : Executor {
       HipCtxRef ctx; BoxedExecutor child; sqlrs_filter_t *f = nullptr; detail::Lowered low;
@@ -452,6 +453,7 @@ struct FilterExecutor { // filter.rs:7-10
     s->ctx = ctx; s->child = std::move(child); s->low = detail::lower(expr); s->group = group; s->depth = depth;
     sqlrs_expr_t e = s->low.abi();
     ctx->check(sqlrs_filter_create(ctx->raw, &e, &s->f));
+    if (async_all_types) ctx->check(sqlrs_filter_set_async_all_types(s->f, 1));
     return s;
   }
 };
@@ -701,6 +703,7 @@ struct ProjectExecutor { // project.rs:6-9
   std::vector<std::string> output_names; // eval_field's names are the caller's business (binder); optional here
   size_t group = 0;                      // child batches per library call (see FilterExecutor)
   size_t depth = 0;                      // sqlrs_project_push_async, that many tickets in flight (see FilterExecutor)
+  bool async_all_types = false;          // sqlrs_project_set_async_all_types: computed columns over Utf8 / Boolean columns in one launch too
   BoxedExecutor execute() {
     struct S : Executor {
       HipCtxRef ctx; BoxedExecutor child; sqlrs_project_t *p = nullptr; std::vector<std::string> names;
@@ -771,6 +774,7 @@ struct ProjectExecutor { // project.rs:6-9
     for (auto &e : exprs) low.push_back(detail::lower(e));
     for (auto &l : low) ex.push_back(l.abi());
     ctx->check(sqlrs_project_create(ctx->raw, (int)ex.size(), ex.data(), &s->p));
+    if (async_all_types) ctx->check(sqlrs_project_set_async_all_types(s->p, 1));
     return s;
   }
 };

@@ -284,11 +284,31 @@ int sqlrs_filter_push_many(sqlrs_filter_t *f, int n, const sqlrs_batch_t *const 
  * utf8 columns under ANY predicate over their int32 / int64 / float64 columns (comparisons, + - * / with the evaluator's wrapping
  * and its "Divide by zero error" — reported by sqlrs_batch_wait of that ticket —, casts between the three types, NULL
  * constants, AND / OR; <= 24 expression nodes) share ONE launch with up to three neighbours and take no copy call (pinned,
- * device-mapped ring); every other batch (a predicate that reads a utf8 / boolean column, DEVICE input, more rows or columns)
- * runs the synchronous operator inside push_async: same batches, no speed-up.  Tickets must be waited for before their ctx is
- * destroyed. */
+ * device-mapped ring); every other batch (DEVICE input, more rows or columns, and — unless
+ * sqlrs_filter_set_async_all_types is on, below — a predicate that reads a utf8 / boolean column or a batch that carries a
+ * boolean column) runs the synchronous operator inside push_async: same batches, no speed-up.  Tickets must be waited for
+ * before their ctx is destroyed. */
 typedef struct sqlrs_ticket sqlrs_ticket_t;
 int sqlrs_filter_push_async(sqlrs_filter_t *f, const sqlrs_batch_t *in, sqlrs_ticket_t **ticket);
+/* on != 0: the one-launch path of sqlrs_filter_push_async takes every column type.  Default 0: exactly the behaviour
+ * described above.  f == NULL: SQLRS_ERR_INTERNAL.  May be called at any time between calls on the filter and affects the
+ * batches pushed afterwards; results never depend on it (the stream of HOST batches is the synchronous operator's, batch
+ * for batch; "Divide by zero error" still arrives at the wait of its own ticket), so there is no ordering rule.
+ *
+ * With the switch on the predicate may also read
+ *   - utf8 columns and utf8 constants (the empty string and a NULL constant included), as operands of the six comparisons
+ *     against another utf8 operand: bytes compare unsigned and lexicographically, a proper prefix is less, a NULL operand
+ *     gives NULL.  A utf8 cast, utf8 arithmetic or a utf8 result is not a program: the synchronous evaluator runs and
+ *     raises whatever there is to raise.  The utf8 constants of one expression may total at most 1024 bytes; more runs the
+ *     synchronous operator;
+ *   - boolean columns, as operands of comparisons (false < true) and of AND / OR, as the source of a cast to int32 / int64 /
+ *     float64, or as the whole predicate (WHERE p);
+ * and the batch may carry boolean columns (compacted like a validity bitmap).  What still sends a HOST batch to the
+ * synchronous operator is size alone: more than 4096 rows, 12 columns, 24 expression nodes or 8 operands in flight, more
+ * than 1024 bytes of utf8 constants, columns (plus constants) that do not fit the 512 KiB of a ring slot's input or output
+ * area, comparison operands of two different types.  A batch with nothing of this in it takes the same kernel as with
+ * the switch off. */
+int sqlrs_filter_set_async_all_types(sqlrs_filter_t *f, int on);
 int sqlrs_batch_wait(sqlrs_ticket_t *ticket, sqlrs_batch_t **out);
 void sqlrs_filter_destroy(sqlrs_filter_t *f);
 
@@ -551,8 +571,16 @@ int sqlrs_project_push_many(sqlrs_project_t *p, int n, const sqlrs_batch_t *cons
 /* sqlrs_project_push without the wait (see sqlrs_filter_push_async; project.rs:15-27 polled one batch at a time): the fast
  * path takes HOST batches of <= 4096 rows whose output columns are bare column references (int32 / int64 / float64 /
  * boolean / utf8) or expressions over int32 / int64 / float64 columns with an int32 / int64 / float64 / boolean result
- * (<= 6 computed columns, <= 12 columns in and out); sqlrs_batch_wait reports a division by zero of that batch. */
+ * (<= 6 computed columns, <= 12 columns in and out); sqlrs_batch_wait reports a division by zero of that batch.  An
+ * expression that reads a utf8 / boolean column runs the synchronous operator inside push_async unless
+ * sqlrs_project_set_async_all_types is on. */
 int sqlrs_project_push_async(sqlrs_project_t *p, const sqlrs_batch_t *in, sqlrs_ticket_t **ticket);
+/* on != 0: the computed columns of sqlrs_project_push_async may read utf8 and boolean columns and utf8 constants, under the
+ * rules of sqlrs_filter_set_async_all_types (utf8 only as comparison operands, <= 1024 bytes of utf8 constants per
+ * expression, boolean columns in comparisons, AND / OR and casts; a computed column is still int32 / int64 / float64 /
+ * boolean).  Default 0: exactly the behaviour described above.  p == NULL: SQLRS_ERR_INTERNAL.  May be called at any time
+ * between calls on the projection; affects the batches pushed afterwards, never their contents. */
+int sqlrs_project_set_async_all_types(sqlrs_project_t *p, int on);
 void sqlrs_project_destroy(sqlrs_project_t *p);
 
 /* [ref: src/executor/limit.rs:4-81  LimitExecutor{limit, offset, child}]  limit / offset are the constants

@@ -388,6 +388,8 @@ class Backend:
             "hash_join_set_async_utf8": (i, [vp, C.c_int]),
             "hash_join_set_async_filter": (i, [vp, C.c_int]),
             "project_push_async": (i, [vp, pb, pvp]),
+            "filter_set_async_all_types": (i, [vp, C.c_int]),
+            "project_set_async_all_types": (i, [vp, C.c_int]),
             "batch_wait": (i, [vp, ppb]),
             "batch_import_arrow": (i, [vp, C.POINTER(ArrowArrayC), C.POINTER(ArrowSchemaC), ppb]),
             "batch_export_arrow": (i, [vp, pb, C.POINTER(C.c_char_p), C.POINTER(ArrowArrayC), C.POINTER(ArrowSchemaC)]),

@@ -64,7 +64,7 @@ int sa_take_slot(SaRing *r) {
 static uint32_t sa_width(int32_t dtype) { return dtype == SQLRS_INT32 ? 4u : (dtype == SQLRS_INT64 || dtype == SQLRS_FLOAT64) ? 8u : 0u; }
 
 bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int first_out_col, const int32_t *front_dtypes, bool allow_utf8,
-                    uint32_t out_rows, const uint64_t *front_bytes) {
+                    uint32_t out_rows, const uint64_t *front_bytes, bool allow_bool, uint32_t extra_bytes, uint32_t *extra_off) {
   if (!in || in->num_rows < 0 || in->num_rows > (int64_t)SA_MAX_ROWS || in->num_columns <= 0 ||
       in->num_columns + first_out_col > SA_MAX_COLS)
     return false;
@@ -78,6 +78,8 @@ bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int f
     if (col.mem != SQLRS_MEM_HOST || col.length != in->num_rows) return false;
     if (col.dtype == SQLRS_UTF8) {
       if (!allow_utf8 || !col.offsets || col.offsets[rows] < col.offsets[0] || (col.offsets[rows] > col.offsets[0] && !col.values)) return false;
+    } else if (col.dtype == SQLRS_BOOLEAN) {
+      if (!allow_bool || (rows && !col.values)) return false;
     } else if (!sa_width(col.dtype) || (rows && !col.values))
       return false;
   }
@@ -89,14 +91,14 @@ bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int f
   for (int c = 0; c < lay->ncols; c++) {
     SaCol &d = lay->c[c];
     d.dtype = c < first_out_col ? front_dtypes[c] : in->columns[c - first_out_col].dtype;
-    const bool utf8 = d.dtype == SQLRS_UTF8;
+    const bool utf8 = d.dtype == SQLRS_UTF8, boolean = d.dtype == SQLRS_BOOLEAN && c >= first_out_col; // (checked above: only with allow_bool)
     d.width = utf8 ? 4u : sa_width(d.dtype);
-    if (!d.width || (utf8 && c < first_out_col && !front_bytes)) return false;
+    if ((!d.width && !boolean) || (utf8 && c < first_out_col && !front_bytes)) return false;
     d.in_off = d.in_voff = d.in_data = d.out_data = SA_NONE;
     d.data_base = d.out_cap = 0;
     const size_t nval = utf8 ? (size_t)rows + 1 : rows, nout = utf8 ? (size_t)out_rows + 1 : out_rows;
     d.out_off = (uint32_t)out_at;
-    out_at = up64(out_at + (size_t)d.width * nout);
+    out_at = up64(out_at + (boolean ? (size_t)out_vbytes + 8 : (size_t)d.width * nout)); // (a Boolean column: its value bitmap, whole words)
     d.out_voff = (uint32_t)out_at;
     out_at = up64(out_at + out_vbytes);
     if (utf8 && c < first_out_col) { // a build column: its bytes stay where they are, the output's are reserved as the caller says
@@ -108,7 +110,7 @@ bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int f
     if (c >= first_out_col) {
       const sqlrs_column_t &col = in->columns[c - first_out_col];
       d.in_off = (uint32_t)in_at;
-      in_at = up64(in_at + (size_t)d.width * nval);
+      in_at = up64(in_at + (boolean ? (size_t)vbytes + 8 : (size_t)d.width * nval));
       if (col.validity && col.null_count != 0) {
         d.in_voff = (uint32_t)in_at;
         in_at = up64(in_at + vbytes + 8); // (+ 8: the kernel may read the bitmap in whole words)
@@ -126,6 +128,8 @@ bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int f
     }
     if (in_at > SA_AREA || out_at > SA_AREA) return false;
   }
+  if (extra_off) *extra_off = (uint32_t)in_at;
+  if (in_at + extra_bytes > SA_AREA) return false;
   for (int c = first_out_col; c < lay->ncols; c++) { // the only copies of the fast path: 4-32 KB per column, host to pinned host
     const sqlrs_column_t &col = in->columns[c - first_out_col];
     const SaCol &d = lay->c[c];
@@ -133,6 +137,8 @@ bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int f
       std::memcpy(area + d.in_off, col.offsets, 4 * ((size_t)rows + 1));
       const size_t nbytes = (size_t)(col.offsets[rows] - col.offsets[0]);
       if (nbytes) std::memcpy(area + d.in_data, (const uint8_t *)col.values + col.offsets[0], nbytes);
+    } else if (d.dtype == SQLRS_BOOLEAN) {
+      if (rows) std::memcpy(area + d.in_off, col.values, vbytes);
     } else if (rows)
       std::memcpy(area + d.in_off, col.values, (size_t)d.width * rows);
     if (d.in_voff != SA_NONE) std::memcpy(area + d.in_voff, col.validity, vbytes);
@@ -140,14 +146,19 @@ bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int f
   return true;
 }
 
-bool sa_compile(const Expr &e, const sqlrs_batch_t *in, SaProgram *out) {
+bool sa_compile(const Expr &e, const sqlrs_batch_t *in, SaProgram *out, bool wide, SaPool *pool) {
   if (!in || in->num_columns < 0) return false;
   std::vector<int32_t> dt((size_t)in->num_columns);
   for (int c = 0; c < in->num_columns; c++) dt[(size_t)c] = in->columns[c].dtype;
-  return sa_compile(e, dt.data(), in->num_columns, out);
+  return sa_compile(e, dt.data(), in->num_columns, out, wide, pool);
 }
-bool sa_compile(const Expr &e, const int32_t *dtypes, int ncols, SaProgram *out) {
+bool sa_compile(const Expr &e, const int32_t *dtypes, int ncols, SaProgram *out, bool wide, SaPool *pool) {
   if (e.nodes.empty() || e.nodes.size() > (size_t)SA_PROG_MAX) return false;
+  if (!pool) wide = false; // (Utf8 constants need their pool)
+  if (pool) {
+    pool->nbytes = 0;
+    pool->wide = false;
+  }
   int32_t st[SA_STACK_MAX];
   int sp = 0;
   out->n = 0;
@@ -159,7 +170,9 @@ bool sa_compile(const Expr &e, const int32_t *dtypes, int ncols, SaProgram *out)
     case SQLRS_EXPR_INPUT_REF: {
       if (n.index < 0 || n.index >= ncols || sp >= SA_STACK_MAX) return false;
       const int32_t d = dtypes[n.index];
-      if (!numeric(d)) return false; // (Boolean columns are bit-packed, Utf8 has no place on this stack)
+      // (Boolean columns are bit-packed, a Utf8 value is {length, offset}: operands only the `wide` evaluator and loader know)
+      if (!numeric(d) && !(wide && (d == SQLRS_BOOLEAN || d == SQLRS_UTF8))) return false;
+      if (!numeric(d)) pool->wide = true;
       I.op = SAO_COL;
       I.dtype = (uint8_t)d;
       I.col = (uint32_t)n.index;
@@ -167,11 +180,18 @@ bool sa_compile(const Expr &e, const int32_t *dtypes, int ncols, SaProgram *out)
       break;
     }
     case SQLRS_EXPR_CONSTANT: {
-      if (sp >= SA_STACK_MAX || !(numeric(n.dtype) || n.dtype == SQLRS_BOOLEAN)) return false;
+      if (sp >= SA_STACK_MAX || !(numeric(n.dtype) || n.dtype == SQLRS_BOOLEAN || (wide && n.dtype == SQLRS_UTF8))) return false;
       I.op = SAO_CONST;
       I.dtype = (uint8_t)n.dtype;
       I.is_null = n.is_null ? 1 : 0;
-      if (n.dtype == SQLRS_FLOAT64) std::memcpy(&I.imm, &n.f, 8);
+      if (n.dtype == SQLRS_UTF8) { // {length, offset in the pool}; a NULL constant: no bytes (make_scalar)
+        const std::string empty, &str = (n.is_null || k >= e.strings.size()) ? empty : e.strings[k];
+        if (str.size() > (size_t)SA_POOL_MAX - pool->nbytes) return false;
+        I.imm = ((unsigned long long)str.size() << 32) | pool->nbytes;
+        std::memcpy(pool->bytes + pool->nbytes, str.data(), str.size());
+        pool->nbytes += (uint32_t)str.size();
+        pool->wide = true;
+      } else if (n.dtype == SQLRS_FLOAT64) std::memcpy(&I.imm, &n.f, 8);
       else if (n.dtype == SQLRS_INT32) I.imm = (unsigned long long)(long long)(int32_t)n.i;
       else if (n.dtype == SQLRS_BOOLEAN) I.imm = n.i ? 1ull : 0ull;
       else I.imm = (unsigned long long)n.i;
@@ -181,6 +201,7 @@ bool sa_compile(const Expr &e, const int32_t *dtypes, int ncols, SaProgram *out)
     case SQLRS_EXPR_TYPE_CAST: {
       if (sp < 1) return false;
       const int32_t from = st[sp - 1], to = n.dtype;
+      if (from == SQLRS_UTF8) return false; // (no Utf8 value leaves the stack but into a comparison)
       if (from == to) continue; // (cast_col: the column as it is)
       if (!numeric(to) || !(numeric(from) || from == SQLRS_BOOLEAN)) return false;
       I.op = SAO_CAST;
@@ -198,7 +219,7 @@ bool sa_compile(const Expr &e, const int32_t *dtypes, int ncols, SaProgram *out)
         I.dtype = (uint8_t)l;
         st[sp - 2] = l;
       } else if (n.op >= SQLRS_EXPR_GT && n.op <= SQLRS_EXPR_NOTEQ) {
-        if (l != r || !(numeric(l) || l == SQLRS_BOOLEAN)) return false;
+        if (l != r || !(numeric(l) || l == SQLRS_BOOLEAN || l == SQLRS_UTF8)) return false; // (a Utf8 operand got here only with `wide`)
         I.op = (uint8_t)(SAO_GT + (n.op - SQLRS_EXPR_GT));
         I.dtype = (uint8_t)l;
         st[sp - 2] = SQLRS_BOOLEAN;

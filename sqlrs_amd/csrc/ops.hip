@@ -21,6 +21,7 @@ struct sqlrs_filter {
   std::unique_ptr<HostStage> stage; // sqlrs_filter_push_many: the calls' small HOST batches, uploaded together
   void *pin_out = nullptr;          // ... and where their kept rows land (pinned: the copy back runs at the PCIe rate)
   size_t pin_cap = 0;
+  bool async_all_types = false; // sqlrs_filter_set_async_all_types: push_async's program reads Utf8 / Boolean columns too
   ~sqlrs_filter() {
     if (pin_out) (void)hipHostFree(pin_out);
   }
@@ -205,6 +206,9 @@ struct SaFilterParams {
   uint8_t *out;
   unsigned long long seq;
 };
+// WIDE (sqlrs_filter_set_async_all_types, chosen per batch by the host): the program may read Utf8 / Boolean columns
+// (sa_eval_row<true>) and a Boolean payload column is compacted bit by bit (sa_pack_bits); the narrow instantiation keeps its code.
+template <bool WIDE>
 __global__ __launch_bounds__(1024) void sa_filter_kernel(SaGroup<SaFilterParams> grp) {
   const SaFilterParams &p = grp.p[blockIdx.x]; // (one workgroup per batch of the group)
   __shared__ uint32_t s_w[17], s_nulls[SA_MAX_COLS];
@@ -220,7 +224,9 @@ __global__ __launch_bounds__(1024) void sa_filter_kernel(SaGroup<SaFilterParams>
       [&](uint32_t r, int) {
         if (p.nterms == 0) { // the general predicate: kept = the program's value is TRUE (NULL -> dropped, filter.rs:16-24)
           bool valid, div0 = false;
-          const unsigned long long v = sa_eval_row(p.prog, p.lay, p.in, r, &valid, &div0);
+          unsigned long long v;
+          if constexpr (WIDE) v = sa_eval_row<true>(p.prog, SaSlotLoadWide{p.lay, p.in, r}, &valid, &div0);
+          else v = sa_eval_row(p.prog, p.lay, p.in, r, &valid, &div0);
           if (div0) s_div0 = 1u;
           return valid && v != 0;
         }
@@ -286,6 +292,27 @@ __global__ __launch_bounds__(1024) void sa_filter_kernel(SaGroup<SaFilterParams>
       else __syncthreads(); // (s_len is reused by the next Utf8 column)
       continue;
     }
+    if constexpr (WIDE) {
+      if (col.dtype == SQLRS_BOOLEAN) { // the kept rows' value bits by output position, packed; then the validity the same way
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+          if (!((bits >> t) & 1)) continue;
+          const uint32_t r = (uint32_t)t * 1024u + threadIdx.x;
+          s_v[pos[t]] = (p.in[col.in_off + (r >> 3)] >> (r & 7)) & 1;
+        }
+        sa_pack_bits(s_v, total, p.out + col.out_off);
+        if (valid) {
+#pragma unroll
+          for (int t = 0; t < 4; t++) {
+            if (!((bits >> t) & 1)) continue;
+            const uint32_t r = (uint32_t)t * 1024u + threadIdx.x;
+            s_v[pos[t]] = (valid[r >> 3] >> (r & 7)) & 1;
+          }
+          sa_pack_validity(s_v, total, p.out + col.out_voff, &s_nulls[c]);
+        }
+        continue;
+      }
+    }
 #pragma unroll
     for (int t = 0; t < 4; t++) {
       if (!((bits >> t) & 1)) continue;
@@ -298,10 +325,10 @@ __global__ __launch_bounds__(1024) void sa_filter_kernel(SaGroup<SaFilterParams>
   }
   sa_publish((SaHeader *)p.out, p.seq, total, s_nulls, p.lay.ncols, &s_div0);
 }
-static void sa_filter_launch(SaRing *r, Ctx *ctx) {
+template <bool WIDE> static void sa_filter_launch(SaRing *r, Ctx *ctx) { // (a group is of ONE launch function: sa_enqueue)
   SaGroup<SaFilterParams> g;
   for (int i = 0; i < r->pend_n; i++) std::memcpy(&g.p[i], r->pend_buf + (size_t)i * SA_PARAM_MAX, sizeof(SaFilterParams));
-  sa_filter_kernel<<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g); // (reads nothing the ctx stream produces)
+  sa_filter_kernel<WIDE><<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g); // (reads nothing the ctx stream produces)
   SQ_HIP(hipGetLastError());
 }
 // the shapes the fast path evaluates: t1 [t2 AND [t3 AND [t4 AND]]] in postfix, every term INPUT_REF CONSTANT CMP over an
@@ -340,10 +367,11 @@ static bool sa_filter_shape(const Expr &e, const sqlrs_batch_t *in, SaFilterPara
   p->nterms = (int)nterms;
   return true;
 }
-// ... and any other predicate over the batch's int32 / int64 / float64 columns, as a postfix program (small_async.hpp)
-static bool sa_filter_program(const Expr &e, const sqlrs_batch_t *in, SaFilterParams *p) {
+// ... and any other predicate over the batch's int32 / int64 / float64 columns — Utf8 and Boolean ones too with `wide`, the Utf8
+// constants in `pool` — as a postfix program (small_async.hpp)
+static bool sa_filter_program(const Expr &e, const sqlrs_batch_t *in, SaFilterParams *p, bool wide, SaPool *pool) {
   p->nterms = 0;
-  return sa_compile(e, in, &p->prog) && p->prog.result_dtype == SQLRS_BOOLEAN;
+  return sa_compile(e, in, &p->prog, wide, pool) && p->prog.result_dtype == SQLRS_BOOLEAN;
 }
 } // namespace sq
 
@@ -361,15 +389,26 @@ int sqlrs_filter_push_async(sqlrs_filter_t *f, const sqlrs_batch_t *in, sqlrs_ti
     t->ctx = ctx;
     SaFilterParams p;
     const char *off_e = hook("SQLRS_ASYNC_FAST"); // test hook, read per call: 0 = every batch through the synchronous operator
-    if (!(off_e && off_e[0] == '0') && (sa_filter_shape(f->expr, in, &p) || sa_filter_program(f->expr, in, &p))) {
+    const bool all_types = f->async_all_types;
+    SaPool pool;
+    if (!(off_e && off_e[0] == '0') && (sa_filter_shape(f->expr, in, &p) || sa_filter_program(f->expr, in, &p, all_types, &pool))) {
       SaRing *r = sa_ring(ctx);
       const int slot = r ? sa_take_slot(r) : -1;
       if (slot >= 0) {
-        if (sa_stage_input(in, r->in_area(slot), &p.lay, 0, nullptr, true)) { // (Utf8 payload columns travel too)
+        const uint32_t pool_bytes = p.nterms ? 0u : pool.nbytes;
+        uint32_t pool_off = 0;
+        // (Utf8 payload columns travel too; Boolean ones and the constant pool behind the switch)
+        if (sa_stage_input(in, r->in_area(slot), &p.lay, 0, nullptr, true, SA_NONE, nullptr, all_types, pool_bytes, &pool_off)) {
+          bool wide = !p.nterms && pool.wide; // the batch's kernel: wide only when the program or a payload column needs it
+          for (int c = 0; c < p.lay.ncols; c++) wide = wide || p.lay.c[c].dtype == SQLRS_BOOLEAN;
+          if (pool_bytes) {
+            std::memcpy(r->in_area(slot) + pool_off, pool.bytes, pool_bytes);
+            sa_place_pool(&p.prog, pool_off);
+          }
           p.in = r->in_area(slot);
           p.out = r->out_area(slot);
           p.seq = ++r->seq;
-          sa_enqueue(ctx, r, f, sa_filter_launch, p, slot);
+          sa_enqueue(ctx, r, f, wide ? sa_filter_launch<true> : sa_filter_launch<false>, p, slot);
           if (p.nterms) ctx->async_conj_batches++; // (sa_filter_shape took it: the program counts in async_fast_batches alone)
           t->slot = slot;
           t->seq = p.seq;
@@ -385,6 +424,14 @@ int sqlrs_filter_push_async(sqlrs_filter_t *f, const sqlrs_batch_t *in, sqlrs_ti
     t->done = emit_batch(ctx, filter_batch(f, ib, nullptr), SQLRS_MEM_HOST);
     *ticket = t.release();
   });
+}
+
+// push_async's one-launch path for predicates that read Utf8 / Boolean columns and batches that carry Boolean ones (small_async.hpp);
+// off = only int32 / int64 / float64 operands.  Affects the batches pushed afterwards; results never depend on it.
+int sqlrs_filter_set_async_all_types(sqlrs_filter_t *f, int on) {
+  if (!f) return SQLRS_ERR_INTERNAL;
+  f->async_all_types = on != 0;
+  return SQLRS_OK;
 }
 
 // n iterations of that loop in one call — out[i] is exactly what sqlrs_filter_push(in[i]) returns (one output batch per

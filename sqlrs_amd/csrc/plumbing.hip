@@ -55,6 +55,7 @@ struct sqlrs_project {
   std::unique_ptr<HostStage> stage; // sqlrs_project_push_many: the call's small HOST batches, uploaded together
   void *pin_out = nullptr;          // ... and where their projected rows land on the host (pinned)
   size_t pin_cap = 0;
+  bool async_all_types = false; // sqlrs_project_set_async_all_types: push_async's programs read Utf8 / Boolean columns too
   ~sqlrs_project() {
     if (pin_out) (void)hipHostFree(pin_out);
   }
@@ -227,7 +228,8 @@ namespace sq {
 // ---- one small HOST batch, one launch, no copy call (small_async.hpp): Project -------------------------------------------------
 // An output column is either a bare InputRef — copied by the HOST into the slot's output area at the push (int32 / int64 /
 // float64 / boolean / utf8: the rows do not move, project.rs:15-27) — or an expression over the batch's int32 / int64 /
-// float64 columns, run per row as a postfix program (sa_eval_row: the evaluator's semantics; int32 / int64 / float64 / boolean
+// float64 columns (Utf8 and Boolean ones too behind sqlrs_project_set_async_all_types: staged like the Filter's, the WIDE
+// instantiation), run per row as a postfix program (sa_eval_row: the evaluator's semantics; int32 / int64 / float64 / boolean
 // results).  A wave owns 64 consecutive rows, so a validity bitmap (and a boolean result) leaves as one ballot word per wave.
 constexpr int SP_PROGS = 6; // computed columns per projection (their programs are copied into LDS: 6 x 392 B)
 struct SaOutCol {
@@ -239,13 +241,15 @@ struct SaOutCol {
 struct SaProjectParams {
   SaLayout lay; // the INPUT columns the programs read (in_off = SA_NONE: not staged)
   int nout, nprog;
-  uint32_t prog_off; // SaProgram[nprog] in the slot's input area
+  uint32_t prog_off; // SaProgram[nprog] in the slot's input area (the programs' Utf8 constants behind them)
+  bool wide;         // a program reads a Utf8 / Boolean column or a Utf8 constant: sa_project_kernel<true>
   SaOutCol oc[SA_MAX_COLS];
   const uint8_t *in;
   uint8_t *out;
   unsigned long long seq;
 };
 static_assert(sizeof(SaProjectParams) <= SA_PARAM_MAX, "parameter block too large");
+template <bool WIDE>
 __global__ __launch_bounds__(1024) void sa_project_kernel(SaGroup<SaProjectParams> grp) {
   const SaProjectParams &p = grp.p[blockIdx.x]; // (one workgroup per batch of the group)
   __shared__ __attribute__((aligned(8))) unsigned char s_prog_raw[SP_PROGS * sizeof(SaProgram)]; // (SaProgram has member initialisers)
@@ -271,7 +275,10 @@ __global__ __launch_bounds__(1024) void sa_project_kernel(SaGroup<SaProjectParam
       const uint32_t r = (uint32_t)t * 1024u + threadIdx.x, wbase = r & ~63u;
       bool valid = false, div0 = false;
       unsigned long long v = 0;
-      if (r < rows) v = sa_eval_row(pr, p.lay, p.in, r, &valid, &div0);
+      if (r < rows) {
+        if constexpr (WIDE) v = sa_eval_row<true>(pr, SaSlotLoadWide{p.lay, p.in, r}, &valid, &div0);
+        else v = sa_eval_row(pr, p.lay, p.in, r, &valid, &div0);
+      }
       if (div0) s_div0 = 1u;
       if (!valid) v = 0; // (the slot of a NULL: zero)
       const uint64_t vm = __ballot(valid);
@@ -291,10 +298,10 @@ __global__ __launch_bounds__(1024) void sa_project_kernel(SaGroup<SaProjectParam
   }
   sa_publish((SaHeader *)p.out, p.seq, rows, s_nulls, p.nout, &s_div0);
 }
-static void sa_project_launch(SaRing *r, Ctx *ctx) {
+template <bool WIDE> static void sa_project_launch(SaRing *r, Ctx *ctx) {
   SaGroup<SaProjectParams> g;
   for (int i = 0; i < r->pend_n; i++) std::memcpy(&g.p[i], r->pend_buf + (size_t)i * SA_PARAM_MAX, sizeof(SaProjectParams));
-  sa_project_kernel<<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g); // (reads nothing the ctx stream produces)
+  sa_project_kernel<WIDE><<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g); // (reads nothing the ctx stream produces)
   SQ_HIP(hipGetLastError());
 }
 // plans the batch (which columns are copied, which computed), lays it out in the slot and copies what the host copies;
@@ -311,9 +318,12 @@ static bool sa_project_stage(const sqlrs_project *pj, const sqlrs_batch_t *in, u
     if (col.mem != SQLRS_MEM_HOST || col.length != in->num_rows) return false;
   }
   SaProgram progs[SP_PROGS];
+  SaPool pools[SP_PROGS]; // (a pool per expression: SA_POOL_MAX bytes each at the most)
+  const bool all_types = pj->async_all_types;
   bool read[SA_MAX_COLS] = {};
   pp->nout = (int)pj->exprs.size();
   pp->nprog = 0;
+  pp->wide = false;
   for (int e = 0; e < pp->nout; e++) {
     const Expr &ex = pj->exprs[(size_t)e];
     SaOutCol &oc = pp->oc[e];
@@ -333,7 +343,8 @@ static bool sa_project_stage(const sqlrs_project *pj, const sqlrs_batch_t *in, u
         return false;
       continue;
     }
-    if (pp->nprog >= SP_PROGS || !sa_compile(ex, in, &progs[pp->nprog])) return false;
+    if (pp->nprog >= SP_PROGS || !sa_compile(ex, in, &progs[pp->nprog], all_types, &pools[pp->nprog])) return false;
+    pp->wide = pp->wide || pools[pp->nprog].wide;
     const SaProgram &pr = progs[pp->nprog];
     oc.prog = pp->nprog++;
     oc.dtype = pr.result_dtype;
@@ -356,16 +367,32 @@ static bool sa_project_stage(const sqlrs_project *pj, const sqlrs_batch_t *in, u
     d.in_off = d.in_voff = d.out_off = d.out_voff = d.in_data = d.out_data = SA_NONE;
     d.data_base = 0;
     if (!read[c]) continue;
-    if (!d.width || (rows && !col.values)) return false; // (sa_compile admits only the fixed-width types)
+    const bool utf8 = col.dtype == SQLRS_UTF8, boolean = col.dtype == SQLRS_BOOLEAN; // (sa_compile admitted them: the switch is on)
+    if (utf8) {
+      if (!col.offsets || col.offsets[rows] < col.offsets[0] || (col.offsets[rows] > col.offsets[0] && !col.values)) return false;
+      d.width = 4;
+    } else if ((!d.width && !boolean) || (rows && !col.values))
+      return false;
     d.in_off = (uint32_t)in_at;
-    in_at = up64(in_at + (size_t)d.width * rows);
+    in_at = up64(in_at + (utf8 ? 4 * ((size_t)rows + 1) : boolean ? (size_t)vbytes + 8 : (size_t)d.width * rows));
     if (col.validity && col.null_count != 0) {
       d.in_voff = (uint32_t)in_at;
       in_at = up64(in_at + vbytes + 8);
     }
+    if (utf8) {
+      d.data_base = (uint32_t)col.offsets[0];
+      d.in_data = (uint32_t)in_at;
+      in_at = up64(in_at + (size_t)(col.offsets[rows] - col.offsets[0]));
+    }
+    if (in_at > SA_AREA) return false;
   }
   pp->prog_off = (uint32_t)in_at;
   in_at = up64(in_at + sizeof(SaProgram) * (size_t)pp->nprog);
+  uint32_t pool_off[SP_PROGS];
+  for (int k = 0; k < pp->nprog; k++) { // the constant pools behind the programs
+    pool_off[k] = (uint32_t)in_at;
+    in_at += pools[k].nbytes;
+  }
   // output area: header | per column values (+ the bytes of a Utf8 column) + validity, whole 64-bit words of bitmap
   size_t out_at = up64(sizeof(SaHeader));
   olay->ncols = pp->nout;
@@ -396,9 +423,21 @@ static bool sa_project_stage(const sqlrs_project *pj, const sqlrs_batch_t *in, u
     const SaCol &d = lay.c[c];
     if (d.in_off == SA_NONE) continue;
     const sqlrs_column_t &col = in->columns[c];
-    if (rows) std::memcpy(in_area + d.in_off, col.values, (size_t)d.width * rows);
+    if (col.dtype == SQLRS_UTF8) {
+      std::memcpy(in_area + d.in_off, col.offsets, 4 * ((size_t)rows + 1));
+      const size_t nbytes = (size_t)(col.offsets[rows] - col.offsets[0]);
+      if (nbytes) std::memcpy(in_area + d.in_data, (const uint8_t *)col.values + col.offsets[0], nbytes);
+    } else if (col.dtype == SQLRS_BOOLEAN) {
+      if (rows) std::memcpy(in_area + d.in_off, col.values, vbytes);
+    } else if (rows)
+      std::memcpy(in_area + d.in_off, col.values, (size_t)d.width * rows);
     if (d.in_voff != SA_NONE) std::memcpy(in_area + d.in_voff, col.validity, vbytes);
   }
+  for (int k = 0; k < pp->nprog; k++)
+    if (pools[k].nbytes) {
+      std::memcpy(in_area + pool_off[k], pools[k].bytes, pools[k].nbytes);
+      sa_place_pool(&progs[k], pool_off[k]);
+    }
   if (pp->nprog) std::memcpy(in_area + pp->prog_off, progs, sizeof(SaProgram) * (size_t)pp->nprog);
   for (int e = 0; e < pp->nout; e++) {
     SaOutCol &oc = pp->oc[e];
@@ -450,7 +489,7 @@ int sqlrs_project_push_async(sqlrs_project_t *p, const sqlrs_batch_t *in, sqlrs_
           pp.in = r->in_area(slot);
           pp.out = r->out_area(slot);
           pp.seq = ++r->seq;
-          sa_enqueue(ctx, r, p, sa_project_launch, pp, slot);
+          sa_enqueue(ctx, r, p, pp.wide ? sa_project_launch<true> : sa_project_launch<false>, pp, slot);
           t->slot = slot;
           t->seq = pp.seq;
           *ticket = t.release();
@@ -464,6 +503,13 @@ int sqlrs_project_push_async(sqlrs_project_t *p, const sqlrs_batch_t *in, sqlrs_
     t->done = emit_batch(ctx, project_batch(p, ib, SQLRS_MEM_HOST), SQLRS_MEM_HOST);
     *ticket = t.release();
   });
+}
+
+// see sqlrs_filter_set_async_all_types: the computed columns' programs read Utf8 / Boolean columns inside the one-launch kernel
+int sqlrs_project_set_async_all_types(sqlrs_project_t *p, int on) {
+  if (!p) return SQLRS_ERR_INTERNAL;
+  p->async_all_types = on != 0;
+  return SQLRS_OK;
 }
 
 int sqlrs_project_push_many(sqlrs_project_t *p, int n, const sqlrs_batch_t *const *in, int out_mem, sqlrs_batch_t **out) {

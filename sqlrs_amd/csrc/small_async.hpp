@@ -12,7 +12,8 @@
 //     writes the output columns + validity bitmaps + a header {sequence number, rows, NULL counts} back into the slot;
 //   * `wait` polls the header's sequence number (system-scope release store behind `__threadfence_system`), falling
 //     back to a stream synchronisation when it does not show up, and copies the rows into an ordinary HOST batch.
-// Anything the fast path does not take — predicates that read a Boolean / Utf8 column or need more than 24 nodes, Utf8
+// Anything the fast path does not take — predicates that read a Boolean / Utf8 column (unless the operator's all-types switch is
+// on, last paragraph but one), a batch that carries a Boolean column (the same switch), predicates of more than 24 nodes, Utf8
 // columns around a join (unless the join's Utf8 switch is on, below), more than 4096 rows, DEVICE input, join filters (unless the join's filter switch is on, last paragraph), NULL probe keys, composite or hash-only join keys,
 // duplicate build keys and outer joins (unless the join's switch is on, next paragraph) — runs the synchronous operator
 // inside push_async and parks the finished batch in the ticket: same results, same one-output-per-input rule, no speed-up.
@@ -33,6 +34,14 @@
 // evaluates it per candidate, compacts the kept candidates into a list in HBM (a region per ring slot), appends the Right / Full
 // probe rows that kept none, and emits from the list — apply_join_filter's order and its visited marks; a valid candidate that
 // divides by zero is SaHeader::pad = 1, the evaluator's error at the wait.  The output bound is the unfiltered one (candidates).
+// sqlrs_filter_set_async_all_types(f, 1) / sqlrs_project_set_async_all_types(p, 1): the program also reads Utf8 and Boolean columns
+// (sa_compile with `wide`, sa_eval_row<true>, SaSlotLoadWide: the `wide` instantiations of sa_filter_kernel / sa_project_kernel, chosen
+// per batch — a batch with nothing wide in it keeps the narrow kernel).  A Utf8 value is ONE stack word {length, byte offset in the slot's
+// input area}: a column's from its staged offsets, a constant's from a pool of at most SA_POOL_MAX bytes per expression that the host stages
+// behind the columns; the six comparisons read both operands' bytes from the slot (cmp_utf8_kernel's order: unsigned bytes, a prefix is
+// less).  A Boolean column is bit r of its staged value bitmap: an operand of comparisons, AND / OR and casts, or the predicate itself.
+// The Filter compacts a Boolean payload column like a validity bitmap (sa_pack_bits).  With the switch on only SIZE sends a HOST batch to
+// the synchronous operator: rows, columns, nodes, stack depth, pool bytes, slot bytes.  (A join's filter keeps the narrow program.)
 #pragma once
 
 #include <cstring>
@@ -124,14 +133,17 @@ template <class P> inline void sa_enqueue(Ctx *ctx, SaRing *r, const void *owner
   if (r->pend_n >= r->group) sa_flush(ctx);
 }
 
-// Lays `in` (HOST columns of int32 / int64 / float64 — and Utf8 when `allow_utf8` — <= SA_MAX_ROWS rows) out in `area` and describes it in `lay`;
+// Lays `in` (HOST columns of int32 / int64 / float64 — Utf8 when `allow_utf8`, Boolean when `allow_bool` — <= SA_MAX_ROWS rows) out in `area` and describes it in `lay`;
 // `first_out_col` output columns are reserved in front of the batch's own (the join's build columns).  `out_rows`: the rows
 // the OUTPUT columns and their bitmaps are laid out for (SA_NONE: as many as the batch has; more for a kernel that emits more
 // rows than it reads — a Utf8 column of the batch then has (its bytes) x (out_rows / rows) reserved: every row emitted equally
 // often at the most).  `front_bytes` (may be null: no Utf8 column in front): the bytes to reserve for the data of front column c
-// when it is Utf8.  false = not a batch for the fast path (nothing written that matters).
+// when it is Utf8.  A Boolean column (width 0) is its value bitmap at in_off and, compacted, at out_off: whole 64-bit words.
+// `extra_bytes` are reserved behind the columns in the input area (a program's constant pool) and *extra_off is where.
+// false = not a batch for the fast path (nothing written that matters).
 bool sa_stage_input(const sqlrs_batch_t *in, uint8_t *area, SaLayout *lay, int first_out_col, const int32_t *front_dtypes,
-                    bool allow_utf8 = false, uint32_t out_rows = SA_NONE, const uint64_t *front_bytes = nullptr);
+                    bool allow_utf8 = false, uint32_t out_rows = SA_NONE, const uint64_t *front_bytes = nullptr, bool allow_bool = false,
+                    uint32_t extra_bytes = 0, uint32_t *extra_off = nullptr);
 
 // ---- a postfix program over the batch's fixed-width columns, evaluated per row INSIDE the one-launch kernels -----------------
 // BoundExpr::eval_column (evaluator.rs:13-28, array_compute.rs:70-90) restated for one row: the same arithmetic (integers wrap,
@@ -149,11 +161,26 @@ struct SaProgram {
   int32_t result_dtype = 0;
   SaInstr ins[SA_PROG_MAX];
 };
-// Expr -> program over the columns of `in`; false = not expressible here (a Utf8 / Boolean column or constant, mixed operand
-// types, an unsupported cast, too long): the synchronous evaluator takes the batch and raises whatever error there is to raise
-bool sa_compile(const Expr &e, const sqlrs_batch_t *in, SaProgram *out);
-// the same over a list of column dtypes (a join's filter: the build side's columns, then the probe side's)
-bool sa_compile(const Expr &e, const int32_t *dtypes, int ncols, SaProgram *out);
+// The Utf8 constants of ONE expression, staged once per batch in the slot's input area: at most SA_POOL_MAX bytes in all (more: the
+// synchronous path).  `wide`: the program has an operand only sa_eval_row<true> knows (a Utf8 / Boolean column, a Utf8 constant).
+constexpr uint32_t SA_POOL_MAX = 1024;
+struct SaPool {
+  uint32_t nbytes = 0;
+  bool wide = false;
+  uint8_t bytes[SA_POOL_MAX];
+};
+// Expr -> program over the columns of `in`; false = not expressible here (a Utf8 / Boolean column or Utf8 constant unless `wide`,
+// mixed operand types, an unsupported cast, too long): the synchronous evaluator takes the batch and raises whatever error there
+// is to raise.  With `wide` (and a pool) a Utf8 column / constant may be an operand of the six comparisons against another Utf8
+// operand — a Utf8 result, cast or arithmetic stays not expressible — and a Boolean column an operand of comparisons, AND / OR and
+// casts, or the whole program.  A Utf8 constant's imm is {length << 32 | offset in the pool}: sa_place_pool makes it a slot offset.
+bool sa_compile(const Expr &e, const sqlrs_batch_t *in, SaProgram *out, bool wide = false, SaPool *pool = nullptr);
+// the same over a list of column dtypes (a join's filter: the build side's columns, then the probe side's — never `wide`)
+bool sa_compile(const Expr &e, const int32_t *dtypes, int ncols, SaProgram *out, bool wide = false, SaPool *pool = nullptr);
+inline void sa_place_pool(SaProgram *pr, uint32_t pool_off) {
+  for (int k = 0; k < pr->n; k++)
+    if (pr->ins[k].op == SAO_CONST && pr->ins[k].dtype == SQLRS_UTF8) pr->ins[k].imm += pool_off;
+}
 
 } // namespace sq
 
@@ -180,9 +207,40 @@ struct SaSlotLoad {
     return c.width == 8 ? ((const unsigned long long *)(in + c.in_off))[r] : (unsigned long long)(long long)((const int32_t *)(in + c.in_off))[r];
   }
 };
+// the same with the all-types operand kinds: a Boolean column is bit r of its value bitmap (0 / 1), a Utf8 column the word
+// {length << 32 | offset of its bytes in the input area}; bytes() is what sa_eval_row<true> compares Utf8 operands through
+struct SaSlotLoadWide {
+  const SaLayout &lay;
+  const uint8_t *in;
+  uint32_t r;
+  __device__ __forceinline__ const uint8_t *bytes() const { return in; }
+  __device__ __forceinline__ unsigned long long operator()(uint32_t col, bool *ok) const {
+    const SaCol &c = lay.c[col];
+    *ok = c.in_voff == SA_NONE || ((in[c.in_voff + (r >> 3)] >> (r & 7)) & 1);
+    if (c.dtype == SQLRS_BOOLEAN) return (unsigned long long)((in[c.in_off + (r >> 3)] >> (r & 7)) & 1);
+    if (c.dtype == SQLRS_UTF8) {
+      const int32_t *off = (const int32_t *)(in + c.in_off);
+      const uint32_t o0 = (uint32_t)off[r], o1 = (uint32_t)off[r + 1];
+      return ((unsigned long long)(o1 - o0) << 32) | (unsigned long long)(c.in_data + (o0 - c.data_base));
+    }
+    return c.width == 8 ? ((const unsigned long long *)(in + c.in_off))[r] : (unsigned long long)(long long)((const int32_t *)(in + c.in_off))[r];
+  }
+};
+// Utf8 operands `a`, `b` ({length << 32 | offset from `base`}) in cmp_utf8_kernel's order: bytes compare unsigned, the shorter string
+// is less when it is a prefix.  `both_valid` false (a NULL operand: the result is NULL whatever the bytes are): no byte is read.
+__device__ __forceinline__ void sa_cmp_utf8(const uint8_t *base, unsigned long long a, unsigned long long b, bool both_valid, bool *lt, bool *eq) {
+  const uint32_t la = (uint32_t)(a >> 32), lb = (uint32_t)(b >> 32), m = both_valid ? (la < lb ? la : lb) : 0u;
+  const uint8_t *pa = base + (uint32_t)a, *pb = base + (uint32_t)b;
+  int c = 0;
+  for (uint32_t i = 0; i < m && c == 0; i++) c = (int)pa[i] - (int)pb[i];
+  if (c == 0) c = (la > lb) - (la < lb);
+  *lt = c < 0;
+  *eq = c == 0;
+}
 // one row of the program: *valid = the result is not NULL; *div0 raised when a valid row divides by zero.  `load(column, &ok)`
-// fetches an operand: SaSlotLoad for the Filter / Project kernels, the joined-row loader of the probe kernels (join.hip)
-template <class Load>
+// fetches an operand: SaSlotLoad for the Filter / Project kernels, the joined-row loader of the probe kernels (join.hip).
+// WIDE (a compile-time flag: the other instantiations keep their code): Utf8 comparisons, through load.bytes() (SaSlotLoadWide)
+template <bool WIDE = false, class Load>
 __device__ __forceinline__ unsigned long long sa_eval_row(const SaProgram &pr, const Load &load, bool *valid, bool *div0) {
   unsigned long long v[SA_STACK_MAX];
   bool ok[SA_STACK_MAX];
@@ -252,7 +310,10 @@ __device__ __forceinline__ unsigned long long sa_eval_row(const SaProgram &pr, c
         }
       } else if (I.op >= SAO_GT && I.op <= SAO_NE) {
         bool lt, eq;
-        if (I.dtype == SQLRS_FLOAT64) {
+        if (WIDE && I.dtype == SQLRS_UTF8) {
+          lt = eq = false;
+          if constexpr (WIDE) sa_cmp_utf8(load.bytes(), a, b, ro, &lt, &eq);
+        } else if (I.dtype == SQLRS_FLOAT64) {
           const unsigned long long x = f64_to_ordered(__longlong_as_double((long long)a)), y = f64_to_ordered(__longlong_as_double((long long)b));
           lt = x < y;
           eq = x == y;
@@ -329,6 +390,20 @@ __device__ __forceinline__ void sa_pack_validity(const uint8_t *s_v, uint32_t to
     out_bits[i] = (uint8_t)byte;
   }
   if (nulls) atomicAdd(s_nulls, nulls);
+  __syncthreads();
+}
+// the same without the count: the VALUE bitmap of a Boolean column the Filter compacts (`s_v[pos]` = the kept row's bit)
+__device__ __forceinline__ void sa_pack_bits(const uint8_t *s_v, uint32_t total, uint8_t *out_bits) {
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < (total + 7) / 8; i += blockDim.x) {
+    uint32_t byte = 0;
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+      const uint32_t p = i * 8 + b;
+      byte |= (p < total ? (uint32_t)s_v[p] : 0u) << b;
+    }
+    out_bits[i] = (uint8_t)byte;
+  }
   __syncthreads();
 }
 // the last step of a fast-path kernel: every thread's stores to the pinned output are pushed out, then ONE thread

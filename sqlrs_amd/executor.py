@@ -82,8 +82,11 @@ class FilterExecutor:
     """``FilterExecutor { expr, child }`` (filter.rs:7-10)."""
 
     def __init__(self, backend: abi.Backend, expr: BoundExpr, child: Iterable,
-                 out_mem: int = abi.MEM_HOST, many: int = 0, depth: int = 0):
+                 out_mem: int = abi.MEM_HOST, many: int = 0, depth: int = 0, async_all_types: bool = False):
         self.backend, self.expr, self.child, self.out_mem = backend, expr, child, out_mem
+        # sqlrs_filter_set_async_all_types: with depth > 0, predicates that read Utf8 / Boolean columns and batches that carry
+        # Boolean columns take one launch per batch too (a backend without the entry point — the oracle — runs unchanged)
+        self.async_all_types = async_all_types
         # depth > 0: sqlrs_filter_push_async with that many tickets in flight — the same stream of HOST batches, the
         # operator polled one batch at a time as the reference does, no stream synchronisation per batch
         self.depth = depth
@@ -116,6 +119,9 @@ class FilterExecutor:
         h = C.c_void_p()
         be.check(be.fn("filter_create")(be.ctx, C.byref(packed.abi), C.byref(h)))
         try:
+            setter = getattr(be.lib, be.prefix + "filter_set_async_all_types", None)
+            if self.async_all_types and setter is not None:
+                be.check(setter(h, 1))
             if self.many > 1 and getattr(be.lib, be.prefix + "filter_push_many", None) is not None:
                 yield from self._execute_many(be, h)
                 return
@@ -402,8 +408,11 @@ class ProjectExecutor:
     """``ProjectExecutor { exprs, child }`` (project.rs:6-9)."""
 
     def __init__(self, backend: abi.Backend, exprs: List[BoundExpr], child: Iterable, out_mem: int = abi.MEM_HOST,
-                 output_names: Optional[Sequence[str]] = None, many: int = 0, depth: int = 0):
+                 output_names: Optional[Sequence[str]] = None, many: int = 0, depth: int = 0, async_all_types: bool = False):
         self.backend, self.exprs, self.child, self.out_mem, self.output_names = backend, exprs, child, out_mem, output_names
+        # sqlrs_project_set_async_all_types: with depth > 0, computed columns that read Utf8 / Boolean columns take one launch
+        # per batch too (see FilterExecutor; a backend without the entry point runs unchanged)
+        self.async_all_types = async_all_types
         self.depth = depth  # > 0: sqlrs_project_push_async with that many tickets in flight (see FilterExecutor)
         # many > 1: that many batches of the child go to sqlrs_project_push_many together (the same stream of output batches,
         # one per input batch, project.rs:15-27)
@@ -415,6 +424,9 @@ class ProjectExecutor:
         h = C.c_void_p()
         be.check(be.fn("project_create")(be.ctx, len(self.exprs), arr, C.byref(h)))
         try:
+            setter = getattr(be.lib, be.prefix + "project_set_async_all_types", None)
+            if self.async_all_types and setter is not None:
+                be.check(setter(h, 1))
             if self.many > 1 and getattr(be.lib, be.prefix + "project_push_many", None) is not None:
                 group = []
 
