@@ -169,8 +169,9 @@ fn join_keys(cond: &JoinCondition) -> Result<(Vec<BoundExpr>, Vec<BoundExpr>, Op
 }
 // (This executor polls through the synchronous sqlrs_hash_join_probe_push.  A caller that polls through
 //  sqlrs_hash_join_probe_push_async instead sets the async switches of ffi.rs right after create and before the first probe
-//  call: sqlrs_hash_join_set_async_general, sqlrs_hash_join_set_async_utf8 and, for a JoinCondition::On with a filter,
-//  sqlrs_hash_join_set_async_filter — each takes the join and 0 / 1.)
+//  call: sqlrs_hash_join_set_async_general, sqlrs_hash_join_set_async_utf8, sqlrs_hash_join_set_async_keys (NULL probe keys,
+//  Utf8 keys, 2 to 4 key columns) and, for a JoinCondition::On with a filter, sqlrs_hash_join_set_async_filter — each takes the
+//  join and 0 / 1.)
 impl HipHashJoinExecutor {
     #[try_stream(boxed, ok = RecordBatch, error = ExecutorError)]
     pub async fn execute(self) {

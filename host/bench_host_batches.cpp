@@ -5,7 +5,10 @@
 //   ./bench_host_batches [rows = 2e7] [groups = 1e6] [batch = 1024]
 //   ./bench_host_batches filter ... | probe ...   the streaming operators at the same batch shape (see bench_filter / bench_probe)
 //   ./bench_host_batches probe_general ...         outer joins / duplicate build keys through push_async (see bench_probe_general)
+//   ./bench_host_batches probe_keys ...            Utf8 keys, two-column keys, NULL probe keys through push_async (see bench_probe_keys)
 //   ./bench_host_batches filter_all_types ...      Utf8 / Boolean predicates through push_async (see bench_filter_all_types)
+#include <dlfcn.h>
+
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -608,6 +611,194 @@ static int bench_probe_general(int argc, char **argv, bool utf8) {
 }
 
 
+// ./bench_host_batches probe_keys [rows = 2e6] [build = 1e6] [batch = 1024] [leg = utf8|pair|nulls|all]
+// sqlrs_hash_join_set_async_keys: three legs over keys the one-launch probe kernels load themselves, each through three paths —
+// sqlrs_hash_join_probe_push per batch, sqlrs_hash_join_probe_push_async with the switch off (the synchronous operator inside
+// push_async: what such a batch cost before) and on (one launch per batch) — DEPTH tickets in flight, off and on alternating in one
+// process, best of 2 after a warm-up each; the joined rows of the three paths must agree.
+//   utf8:  Inner join over unique Utf8 keys of 8-16 bytes (8 hex digits of the key, then 0-8 letters); build (s, p), probe (t, k)
+//   pair:  Left join over a two-column (int64, int64) key (k, 7 k + 3); build (a, b, p), probe (a, b, v)
+//   nulls: Inner join over an int64 key, 5 % of the probe keys NULL (the build side has no NULL key); build (k, p), probe (k, v)
+// A fifth of the probe keys has no partner.  sqlrs_hash_join_set_async_general and _utf8 are on in both push_async paths.  The
+// setter is looked up at run time, so the tool also links against a library that does not have it yet (the other modes).
+static int bench_probe_keys(int argc, char **argv) {
+  const int64_t n = argc > 2 ? (int64_t)std::atof(argv[2]) : 2000000, nB = argc > 3 ? (int64_t)std::atof(argv[3]) : 1000000;
+  const int64_t B = argc > 4 ? std::atoll(argv[4]) : 1024;
+  const char *which = argc > 5 ? argv[5] : "all";
+  sqlrs_ctx_t *ctx = nullptr;
+  typedef int (*setter_t)(sqlrs_hash_join_t *, int);
+  const setter_t set_keys = (setter_t)dlsym(RTLD_DEFAULT, "sqlrs_hash_join_set_async_keys");
+  if (!set_keys || B % 8 != 0 || n * 16 > 2000000000ll) {
+    std::printf("{\"error\": \"probe_keys: needs sqlrs_hash_join_set_async_keys, a batch size that is a multiple of 8 and at most 1.25e8 probe rows\"}\n");
+    return 2;
+  }
+  if (sqlrs_ctx_create(0, &ctx) != SQLRS_OK) {
+    std::printf("{\"error\": \"no device\"}\n");
+    return 2;
+  }
+  std::vector<int64_t> dk((size_t)nB), dk2((size_t)nB), dp((size_t)nB), fk((size_t)n), fk2((size_t)n);
+  std::vector<double> fv((size_t)n);
+  std::vector<uint8_t> fvalid((size_t)(n + 7) / 8 + 8, 0);
+  std::vector<int64_t> fnulls((size_t)((n + B - 1) / B), 0);
+  for (int64_t i = 0; i < nB; i++) {
+    dk[(size_t)i] = (i * 7919) % nB;
+    dk2[(size_t)i] = dk[(size_t)i] * 7 + 3;
+    dp[(size_t)i] = dk[(size_t)i] * 3 + 1;
+  }
+  for (int64_t i = 0; i < n; i++) {
+    fk[(size_t)i] = (int64_t)(splitmix64(0xF1, (uint64_t)i) % (uint64_t)(nB + nB / 4));
+    fk2[(size_t)i] = fk[(size_t)i] * 7 + 3;
+    fv[(size_t)i] = (double)(splitmix64(0xF2, (uint64_t)i) >> 11) * (1.0 / 9007199254740992.0);
+    const bool null = splitmix64(0xF3, (uint64_t)i) % 20 == 0;
+    if (!null) fvalid[(size_t)(i >> 3)] |= (uint8_t)(1u << (i & 7));
+    else fnulls[(size_t)(i / B)]++;
+  }
+  std::vector<int32_t> doff, foff;
+  std::vector<char> dbytes, fbytes;
+  auto strings = [](const std::vector<int64_t> &keys, std::vector<int32_t> &off, std::vector<char> &bytes) {
+    off.resize(keys.size() + 1);
+    off[0] = 0;
+    for (size_t i = 0; i < keys.size(); i++) off[i + 1] = off[i] + 8 + (int32_t)(keys[i] % 9);
+    bytes.resize((size_t)off[keys.size()] + 16);
+    for (size_t i = 0; i < keys.size(); i++) {
+      char hex[17];
+      std::snprintf(hex, sizeof(hex), "%08llx", (unsigned long long)keys[i]);
+      std::memset(bytes.data() + off[i], 'a' + (int)(keys[i] % 26), (size_t)(off[i + 1] - off[i]));
+      std::memcpy(bytes.data() + off[i], hex, 8);
+    }
+  };
+  strings(dk, doff, dbytes);
+  strings(fk, foff, fbytes);
+  sqlrs_expr_node_t k0{}, k1{};
+  k0.op = k1.op = SQLRS_EXPR_INPUT_REF;
+  k0.index = 0;
+  k1.index = 1;
+  sqlrs_expr_t keys2[2] = {{&k0, 1, 0}, {&k1, 1, 0}};
+  const int DEPTH = 8;
+  const int64_t nb = (n + B - 1) / B;
+  int rc_all = 0;
+  for (int leg = 0; leg < 3; leg++) {
+    const char *lname = leg == 0 ? "utf8" : leg == 1 ? "pair" : "nulls";
+    if (std::strcmp(which, "all") != 0 && std::strcmp(which, lname) != 0) continue;
+    const int jt = leg == 1 ? SQLRS_JOIN_LEFT : SQLRS_JOIN_INNER;
+    const int nkey = leg == 1 ? 2 : 1, nlc = leg == 1 ? 3 : 2, nrc = leg == 1 ? 3 : 2;
+    const int32_t rd_utf8[2] = {SQLRS_UTF8, SQLRS_INT64}, rd_pair[3] = {SQLRS_INT64, SQLRS_INT64, SQLRS_FLOAT64}, rd_nulls[2] = {SQLRS_INT64, SQLRS_FLOAT64};
+    const int32_t *rd = leg == 0 ? rd_utf8 : leg == 1 ? rd_pair : rd_nulls;
+    double best[3] = {1e30, 1e30, 1e30}; // push, push_async switch off, push_async switch on
+    int64_t joined[3] = {0, 0, 0};
+    bool ok = true;
+    auto run = [&](int path, int rep) -> int { // 0 ok
+      auto t0 = std::chrono::steady_clock::now();
+      sqlrs_hash_join_t *j = nullptr;
+      CHECK(sqlrs_hash_join_create(ctx, jt, nkey, keys2, keys2, nullptr, nrc, rd, &j));
+      if (path) {
+        CHECK(sqlrs_hash_join_set_async_general(j, 1));
+        CHECK(sqlrs_hash_join_set_async_utf8(j, 1));
+      }
+      if (path == 2) CHECK(set_keys(j, 1));
+      sqlrs_column_t lc[3];
+      if (leg == 0) {
+        host_col(lc[0], SQLRS_UTF8, dbytes.data(), nB);
+        lc[0].offsets = doff.data();
+        host_col(lc[1], SQLRS_INT64, dp.data(), nB);
+      } else {
+        host_col(lc[0], SQLRS_INT64, dk.data(), nB);
+        if (leg == 1) host_col(lc[1], SQLRS_INT64, dk2.data(), nB);
+        host_col(lc[nlc - 1], SQLRS_INT64, dp.data(), nB);
+      }
+      sqlrs_batch_t lb{};
+      lb.num_rows = nB;
+      lb.num_columns = nlc;
+      lb.columns = lc;
+      CHECK(sqlrs_hash_join_build_push(j, &lb));
+      CHECK(sqlrs_hash_join_build_finish(j));
+      int64_t got = 0;
+      auto consume = [&](sqlrs_batch_t *o) { // a matched row carries payload 3 * key + 1 beside the probe row's key
+        if (!o) return;
+        if (rep == 0 && o->num_rows) {
+          const int pc = nlc - 1, kc = leg == 0 ? nlc + 1 : nlc; // payload; the probe row's int64 key
+          const int64_t *p = (const int64_t *)o->columns[pc].values, *rk = (const int64_t *)o->columns[kc].values;
+          const uint8_t *pv = (const uint8_t *)o->columns[pc].validity, *kv = (const uint8_t *)o->columns[kc].validity;
+          for (int64_t r = 0; r < o->num_rows; r += 97) {
+            const bool knull = kv && o->columns[kc].null_count && !((kv[r >> 3] >> (r & 7)) & 1);
+            const bool matched = !knull && rk[r] < nB;
+            const bool valid = !pv || !o->columns[pc].null_count || ((pv[r >> 3] >> (r & 7)) & 1);
+            ok = ok && matched == valid && (!matched || p[r] == 3 * rk[r] + 1) && (jt == SQLRS_JOIN_LEFT || matched);
+          }
+        }
+        got += o->num_rows;
+        sqlrs_batch_release(o);
+      };
+      std::vector<sqlrs_ticket_t *> q((size_t)DEPTH, nullptr);
+      for (int64_t b = 0; b < nb + (path ? DEPTH : 0); b++) {
+        if (path && b >= DEPTH) {
+          sqlrs_batch_t *o = nullptr;
+          CHECK(sqlrs_batch_wait(q[(size_t)(b % DEPTH)], &o));
+          consume(o);
+        }
+        if (b >= nb) continue;
+        const int64_t lo = b * B, m = std::min<int64_t>(B, n - lo);
+        sqlrs_column_t rc[3];
+        if (leg == 0) {
+          host_col(rc[0], SQLRS_UTF8, fbytes.data(), m);
+          rc[0].offsets = foff.data() + lo;
+          host_col(rc[1], SQLRS_INT64, fk.data() + lo, m);
+        } else {
+          host_col(rc[0], SQLRS_INT64, fk.data() + lo, m);
+          if (leg == 1) host_col(rc[1], SQLRS_INT64, fk2.data() + lo, m);
+          host_col(rc[nrc - 1], SQLRS_FLOAT64, fv.data() + lo, m);
+          if (leg == 2) {
+            rc[0].validity = fvalid.data() + lo / 8;
+            rc[0].null_count = fnulls[(size_t)b];
+          }
+        }
+        sqlrs_batch_t rb{};
+        rb.num_rows = m;
+        rb.num_columns = nrc;
+        rb.columns = rc;
+        if (path) {
+          CHECK(sqlrs_hash_join_probe_push_async(j, &rb, &q[(size_t)(b % DEPTH)]));
+        } else {
+          sqlrs_batch_t *o = nullptr;
+          CHECK(sqlrs_hash_join_probe_push(j, &rb, SQLRS_MEM_HOST, &o));
+          consume(o);
+        }
+      }
+      sqlrs_batch_t *tail = nullptr;
+      CHECK(sqlrs_hash_join_finish(j, SQLRS_MEM_HOST, &tail));
+      if (tail) {
+        got += tail->num_rows;
+        sqlrs_batch_release(tail);
+      }
+      sqlrs_hash_join_destroy(j);
+      const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      joined[path] = got;
+      if (rep > 0 && ms < best[path]) best[path] = ms;
+      return 0;
+    };
+    for (int rep = 0; rep < 3; rep++)
+      if (run(0, rep)) return 1;
+    for (int rep = 0; rep < 3; rep++) // off and on alternate
+      for (int path = 1; path <= 2; path++)
+        if (run(path, rep)) return 1;
+    ok = ok && joined[0] == joined[1] && joined[1] == joined[2] && joined[0] > 0;
+    std::printf("{\"mode\": \"probe_keys\", \"leg\": \"%s\", \"join\": \"%s\", \"probe_rows\": %lld, \"build_rows\": %lld, \"batch_rows\": %lld, "
+                "\"joined\": %lld, \"depth\": %d, \"ms_push\": %.1f, \"Mrows_s_push\": %.1f, \"ms_push_async_off\": %.1f, \"Mrows_s_push_async_off\": %.1f, "
+                "\"ms_push_async_on\": %.1f, \"Mrows_s_push_async_on\": %.1f, \"on_over_off\": %.2f, \"check\": \"%s\", \"note\": \"native caller "
+                "(C ABI): build side one host batch of unique keys, probe side pageable %lld-row host batches (a fifth of the keys without partner%s), "
+                "joined batches on the host; push = sqlrs_hash_join_probe_push per batch, push_async_off / _on = sqlrs_hash_join_probe_push_async with "
+                "sqlrs_hash_join_set_async_keys 0 / 1 (alternating runs; _general and _utf8 on in both); Mrows/s = probe rows; build included; best of 2 "
+                "after a warm-up\"}\n",
+                lname, jt == SQLRS_JOIN_LEFT ? "left" : "inner", (long long)n, (long long)nB, (long long)B, (long long)joined[0], DEPTH, best[0],
+                (double)n / best[0] / 1e3, best[1], (double)n / best[1] / 1e3, best[2], (double)n / best[2] / 1e3, best[1] / best[2], ok ? "OK" : "mismatch",
+                (long long)B, leg == 2 ? ", 5 % of them NULL" : "");
+    std::fflush(stdout);
+    if (!ok) rc_all = 1;
+  }
+  sqlrs_ctx_destroy(ctx);
+  return rc_all;
+}
+
 // ./bench_host_batches probe_filter [rows = 2e7] [build = 1e6] [batch = 1024] [join = inner|left|right|full] [dup = 1|4]
 // The probe stream of probe_general with a join filter, ON l.k = r.k AND l.x > r.v over two float64 payload columns (uniform in
 // [0, 1): about half the pairs pass), through three paths: sqlrs_hash_join_probe_push per batch, and
@@ -911,6 +1102,7 @@ static int bench_filter_all_types(int argc, char **argv) {
 int main(int argc, char **argv) {
   if (argc > 1 && std::strcmp(argv[1], "filter_all_types") == 0) return bench_filter_all_types(argc, argv);
   if (argc > 1 && std::strcmp(argv[1], "probe_filter") == 0) return bench_probe_filter(argc, argv);
+  if (argc > 1 && std::strcmp(argv[1], "probe_keys") == 0) return bench_probe_keys(argc, argv);
   if (argc > 1 && std::strcmp(argv[1], "probe_general") == 0) return bench_probe_general(argc, argv, false);
   if (argc > 1 && std::strcmp(argv[1], "probe_utf8") == 0) return bench_probe_general(argc, argv, true);
   if (argc > 1 && std::strcmp(argv[1], "filter") == 0) return bench_filter(argc, argv);

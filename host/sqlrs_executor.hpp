@@ -470,6 +470,7 @@ struct HashJoinExecutor { // hash_join.rs:16-23
   bool async_general = false; // sqlrs_hash_join_set_async_general: with depth > 0, outer joins and duplicate build keys in one launch per batch too
   bool async_utf8 = false;    // sqlrs_hash_join_set_async_utf8: with depth > 0, batches with Utf8 payload columns on either side in one launch too
   bool async_filter = false;  // sqlrs_hash_join_set_async_filter: with depth > 0, a join with a join filter in one launch per batch too (the filter inside the kernel)
+  bool async_keys = false;    // sqlrs_hash_join_set_async_keys: with depth > 0, NULL probe keys, Utf8 keys (with async_utf8) and 2 to 4 key columns in one launch per batch too
 
   BoxedExecutor execute() {
     struct S : Executor {
@@ -561,6 +562,7 @@ struct HashJoinExecutor { // hash_join.rs:16-23
     if (async_general) ctx->check(sqlrs_hash_join_set_async_general(s->j, 1));
     if (async_utf8) ctx->check(sqlrs_hash_join_set_async_utf8(s->j, 1));
     if (async_filter) ctx->check(sqlrs_hash_join_set_async_filter(s->j, 1));
+    if (async_keys) ctx->check(sqlrs_hash_join_set_async_keys(s->j, 1));
     return s;
   }
 };

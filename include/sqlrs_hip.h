@@ -371,8 +371,9 @@ int sqlrs_hash_join_probe_push_async(sqlrs_hash_join_t *j, const sqlrs_batch_t *
  *   and <= 12 columns).
  * M is computed once per join (one small kernel, one fetch) when it is first needed.  The decision is made on the host
  * before a slot is taken; there is no overflow and no re-run.  An Inner join over unique build keys keeps the kernel of
- * the fast path above.  Every other batch — NULL probe keys, join filters, Utf8 / Boolean columns on either side,
- * composite keys, match-by-hash, DEVICE input, more than 4096 rows, the bound exceeded — runs the synchronous operator
+ * the fast path above.  Every other batch — join filters, Utf8 / Boolean columns on either side, DEVICE input, more than
+ * 4096 rows, the bound exceeded, and (unless sqlrs_hash_join_set_async_keys is on, below) NULL probe keys, Utf8 keys and
+ * keys of several columns — runs the synchronous operator
  * inside push_async, as with the switch off.  Left / Full: sqlrs_hash_join_finish may be called with tickets still
  * outstanding; it waits for the queued probe kernels (which mark the visited build rows) before it reads the marks. */
 int sqlrs_hash_join_set_async_general(sqlrs_hash_join_t *j, int on);
@@ -398,7 +399,8 @@ int sqlrs_hash_join_set_async_general(sqlrs_hash_join_t *j, int on);
  * Lmax_c is computed once per join (one small kernel over the build column's offsets and one fetch) when it is first
  * needed.  The host decides before it takes a slot; nothing overflows and nothing is re-run (the kernels compare every
  * column's bytes with its reservation before they store one, and sqlrs_batch_wait reports SQLRS_ERR_INTERNAL should that
- * ever fail).  Everything else — the bound exceeded, Boolean columns, a Utf8 key, and the rest of the lists above — runs
+ * ever fail).  Everything else — the bound exceeded, Boolean columns, a Utf8 key (unless sqlrs_hash_join_set_async_keys is
+ * on as well), and the rest of the lists above — runs
  * the synchronous operator inside push_async, as with the switch off. */
 int sqlrs_hash_join_set_async_utf8(sqlrs_hash_join_t *j, int on);
 /* on != 0: both one-launch kernels of sqlrs_hash_join_probe_push_async also serve a join that HAS a join filter
@@ -430,6 +432,33 @@ int sqlrs_hash_join_set_async_utf8(sqlrs_hash_join_t *j, int on);
  * sqlrs_batch_wait return SQLRS_ERR_ARROW "Divide by zero error"; the batch marks no build row visited, later tickets
  * are unaffected. */
 int sqlrs_hash_join_set_async_filter(sqlrs_hash_join_t *j, int on);
+/* on != 0: both one-launch kernels of sqlrs_hash_join_probe_push_async load the KEY of a probe row themselves: NULL probe
+ * keys, Utf8 keys and keys of 2 to 4 columns take a kernel too.  Default 0: exactly today's behaviour.  Calling rules as
+ * for sqlrs_hash_join_set_async_general (after create, before the first probe call of any kind; later: SQLRS_ERR_INTERNAL;
+ * j == NULL: SQLRS_ERR_INTERNAL); it composes with the three switches above; the contract of probe_push_async is unchanged
+ * (the ticket stands for the HOST batch sqlrs_hash_join_probe_push would have returned, bit for bit, the visited marks
+ * behind the Left / Full tail included).
+ *
+ * Eligibility of a probe batch with the switch on: every condition of the fast path of probe_push_async — or of the
+ * general path when sqlrs_hash_join_set_async_general is on; with Utf8 payload columns when
+ * sqlrs_hash_join_set_async_utf8 is on; with a join filter when sqlrs_hash_join_set_async_filter is on — except "ONE
+ * exactly compared INPUT_REF key of int32 / int64 / float64" and "no NULL probe key in the batch".  In their place:
+ *   KEY COUNT AND TYPE: the join has 1 to 4 key pairs, and every right key expression is a bare INPUT_REF to a column of
+ *   the batch of dtype int32 / int64 / float64 / Utf8;
+ *   UTF8 KEYS: a Utf8 key column needs sqlrs_hash_join_set_async_utf8 on as well — it travels as the payload column it
+ *   already is, under that switch's conditions on `offsets` / `values` and its byte bounds;
+ *   NULLS: probe key columns may hold NULLs.
+ * A join over ONE fixed-width key is compared exactly, as before: the batch's key column has the build key's dtype (any
+ * other stays with the synchronous operator, which refuses it), and a NULL probe key finds the build rows whose key is
+ * NULL (hash_utils.rs:91-104).  A Utf8 key and keys of 2 to 4 columns are matched BY HASH: the kernel computes, per probe
+ * row, the 64-bit value the synchronous operator computes (a NULL column leaves the running hash alone; a value is hashed
+ * under its own column's dtype, so an int32 probe column against an int64 build column finds nothing) and looks it up —
+ * the synchronous route's rule and the reference's (hash_join.rs:222-232), false matches by hash collision included.
+ * Everything else is unchanged: the Inner / unique route versus the general route, the output bound rows x M (M counts
+ * NULL-key build rows as sharing one key; for hashed keys, build rows that share one hash), the byte bounds, the
+ * filter's compile rule.  Still synchronous: Boolean keys, key expressions that are not bare column references, more
+ * than four key columns, the opt-in composite key (SQLRS_JOIN_COMPOSITE=1), and the rest of the lists above. */
+int sqlrs_hash_join_set_async_keys(sqlrs_hash_join_t *j, int on);
 /* The index-pair form of one probe batch, before any gather: 2 columns
  * (UINT64 left index, nullable; UINT32 right index), in the reference's order
  * (probe-row major, build insertion order minor), join filter NOT applied.

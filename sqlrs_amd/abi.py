@@ -387,6 +387,7 @@ class Backend:
             "hash_join_set_async_general": (i, [vp, C.c_int]),
             "hash_join_set_async_utf8": (i, [vp, C.c_int]),
             "hash_join_set_async_filter": (i, [vp, C.c_int]),
+            "hash_join_set_async_keys": (i, [vp, C.c_int]),
             "project_push_async": (i, [vp, pb, pvp]),
             "filter_set_async_all_types": (i, [vp, C.c_int]),
             "project_set_async_all_types": (i, [vp, C.c_int]),

@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "key_hash.hpp" // mix64 (host and device: one definition)
+
 namespace sq {
 
 // two 8-byte words moved with one 16-byte load / store (a {key|row word, value} record)
@@ -179,15 +181,6 @@ __device__ __forceinline__ uint64_t wave_iscan_u64(uint64_t v) {
     if (lane >= d) v += t;
   }
   return v;
-}
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdULL;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ULL;
-  x ^= x >> 33;
-  return x;
 }
 
 // ------------------------------------------------- decoupled look-back (tiles) --

@@ -23,6 +23,7 @@
 #include "prims.hpp"
 #include "small_async.hpp"
 #include "join_kernels.hpp"
+#include "key_hash.hpp"
 #include "join_state.hpp"
 
 #include "join_probe_kernels.hpp" // every kernel of this operator (namespace sq)
@@ -1264,10 +1265,47 @@ __device__ __forceinline__ void sa_load_program(const SaProgram *from, unsigned 
   static_assert(sizeof(SaProgram) % 4 == 0, "copied in words");
   for (uint32_t i = threadIdx.x; i < (uint32_t)(sizeof(SaProgram) / 4); i += blockDim.x) ((uint32_t *)s_raw)[i] = ((const uint32_t *)from)[i];
 }
-template <bool UTF8, bool FILTER> using SaProbeP =
-    std::conditional_t<FILTER, SaWithFilter<std::conditional_t<UTF8, SaProbeUtf8Params, SaProbeParams>>, std::conditional_t<UTF8, SaProbeUtf8Params, SaProbeParams>>;
-template <bool UTF8, bool FILTER>
-__global__ __launch_bounds__(1024) void sa_probe_kernel(SaGroup<SaProbeP<UTF8, FILTER>> grp) {
+// sqlrs_hash_join_set_async_keys (KEYS = true, only together with UTF8 = true; a batch that needs neither a NULL key nor a hashed
+// key keeps the instantiation it always had): the key of a probe row through sa_probe_key.  nkeys = 0, EXACT mode (j->exact: one
+// fixed-width key column, key_col): the value as always, and a row whose validity bit is clear is a NULL key — it takes the NULL
+// build row(s): table[cap] of the slot table (probe_slot(.., is_null)), dt.null_head of the direct-address table, nothing on
+// dd_table (only built without a NULL build key).  nkeys = 1 .. 4, HASH mode (!j->exact: a Utf8 key, or several key columns): the
+// u64 normalize_keys (keys.hip) gives the row, by key_hash.hpp's arithmetic over the columns staged in the slot (key column k =
+// byte k of key_cols) — a NULL leaves the running hash alone, the tag follows the probe column's own dtype — looked up as a
+// value: match-by-hash, the synchronous route's rule and the reference's (hash_join.rs:222-232).
+template <class Base> struct SaWithKeys : Base {
+  int nkeys;
+  uint32_t key_cols;
+};
+template <bool KEYS, class P> __device__ __forceinline__ uint64_t sa_probe_key(const P &p, const SaCol &kc, uint32_t r, bool *is_null) {
+  *is_null = false;
+  if constexpr (KEYS) {
+    if (p.nkeys) {
+      uint64_t acc = 0;
+      for (int k = 0; k < p.nkeys; k++) {
+        const SaCol &c = p.lay.c[p.nleft + (int)((p.key_cols >> (8 * k)) & 0xffu)];
+        if (c.in_voff != SA_NONE && !((p.in[c.in_voff + (r >> 3)] >> (r & 7)) & 1)) continue;
+        uint64_t v;
+        if (c.dtype == SQLRS_UTF8) { // (the bytes sit at in_data from offsets[0] on)
+          const int32_t *off = (const int32_t *)(p.in + c.in_off);
+          v = key_hash_utf8(p.in + c.in_data, (int64_t)((uint32_t)off[r] - c.data_base), (int64_t)((uint32_t)off[r + 1] - c.data_base));
+        } else if (c.width == 8)
+          v = key_hash_fixed(((const uint64_t *)(p.in + c.in_off))[r], KEY_TAG_64);
+        else
+          v = key_hash_fixed((uint64_t)((const uint32_t *)(p.in + c.in_off))[r], KEY_TAG_32);
+        acc = key_fold(v, acc, p.nkeys > 1);
+      }
+      return acc;
+    }
+    *is_null = kc.in_voff != SA_NONE && !((p.in[kc.in_voff + (r >> 3)] >> (r & 7)) & 1);
+  }
+  return p.key_is32 ? (uint64_t)(int64_t)((const int32_t *)(p.in + kc.in_off))[r] : ((const uint64_t *)(p.in + kc.in_off))[r];
+}
+template <bool UTF8, bool FILTER, bool KEYS> using SaProbeBaseP = std::conditional_t<KEYS, SaWithKeys<SaProbeUtf8Params>, std::conditional_t<UTF8, SaProbeUtf8Params, SaProbeParams>>;
+template <bool UTF8, bool FILTER, bool KEYS = false> using SaProbeP = std::conditional_t<FILTER, SaWithFilter<SaProbeBaseP<UTF8, FILTER, KEYS>>, SaProbeBaseP<UTF8, FILTER, KEYS>>;
+template <bool UTF8, bool FILTER, bool KEYS = false>
+__global__ __launch_bounds__(1024) void sa_probe_kernel(SaGroup<SaProbeP<UTF8, FILTER, KEYS>> grp) {
+  static_assert(!KEYS || UTF8, "the key loader is instantiated with the Utf8 kernels only");
   const auto &p = grp.p[blockIdx.x]; // (one workgroup per batch of the group)
   __shared__ uint32_t s_w[17], s_nulls[SA_MAX_COLS];
   __shared__ uint8_t s_v[SA_MAX_ROWS];
@@ -1279,24 +1317,26 @@ __global__ __launch_bounds__(1024) void sa_probe_kernel(SaGroup<SaProbeP<UTF8, F
     if (threadIdx.x == 0) s_div0 = 0;
     __syncthreads();
   }
-  const SaCol &kc = p.lay.c[p.nleft + p.key_col];
+  const SaCol &kc = p.lay.c[p.nleft + p.key_col]; // (the first key column)
   uint32_t m[4] = {DENSE_EMPTY, DENSE_EMPTY, DENSE_EMPTY, DENSE_EMPTY}, pos[4], total;
   const uint32_t bits = sa_positions(
       p.lay.rows,
       [&](uint32_t r, int t) {
-        const uint64_t key = p.key_is32 ? (uint64_t)(int64_t)((const int32_t *)(p.in + kc.in_off))[r] : ((const uint64_t *)(p.in + kc.in_off))[r];
+        bool is_null;
+        const uint64_t key = sa_probe_key<KEYS>(p, kc, r, &is_null);
         uint32_t h = DENSE_EMPTY;
         if (p.dense) {
           const uint64_t d = key - p.dt.kmin;
-          h = dense_get(p.dt, d < p.dt.range ? d : p.dt.range + 1);
+          if (KEYS && is_null) h = p.dt.null_head;
+          else h = dense_get(p.dt, d < p.dt.range ? d : p.dt.range + 1);
         } else {
-          const Slot sl = probe_slot(p.table, p.mask, key, false);
+          const Slot sl = probe_slot(p.table, p.mask, key, KEYS && is_null);
           if (sl.count) h = sl.head;
         }
         if constexpr (FILTER) {
           if (h != DENSE_EMPTY) { // a candidate pair: kept iff the filter is valid and TRUE on the joined row (a NULL drops it)
             bool valid, div0 = false;
-            const unsigned long long v = sa_eval_row(*(const SaProgram *)s_prog_raw, SaJoinedLoad<SaProbeP<UTF8, FILTER>>{p, r, h}, &valid, &div0);
+            const unsigned long long v = sa_eval_row(*(const SaProgram *)s_prog_raw, SaJoinedLoad<SaProbeP<UTF8, FILTER, KEYS>>{p, r, h}, &valid, &div0);
             if (div0) s_div0 = 1u;
             if (!(valid && v != 0)) h = DENSE_EMPTY;
           }
@@ -1400,11 +1440,12 @@ __global__ __launch_bounds__(1024) void sa_probe_kernel(SaGroup<SaProbeP<UTF8, F
   } else
     sa_publish((SaHeader *)p.out, p.seq, total, s_nulls, p.lay.ncols);
 }
-template <bool UTF8, bool FILTER = false> static void sa_probe_launch(SaRing *r, Ctx *ctx) {
-  using P = SaProbeP<UTF8, FILTER>;
+template <bool UTF8, bool FILTER = false, bool KEYS = false> static void sa_probe_launch(SaRing *r, Ctx *ctx) {
+  using P = SaProbeP<UTF8, FILTER, KEYS>;
+  static_assert(sizeof(P) <= SA_PARAM_MAX, "parameter block too large");
   SaGroup<P> g;
   for (int i = 0; i < r->pend_n; i++) std::memcpy(&g.p[i], r->pend_buf + (size_t)i * SA_PARAM_MAX, sizeof(P));
-  sa_probe_kernel<UTF8, FILTER><<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g);
+  sa_probe_kernel<UTF8, FILTER, KEYS><<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g);
   SQ_HIP(hipGetLastError());
 }
 // Lmax of every Utf8 build column: the longest string in bytes, NULL slots included — what one output row can cost at the most
@@ -1497,21 +1538,52 @@ static void sa_probe_filter_device(sqlrs_hash_join *j, bool pairs) {
   }
   if (pairs && !j->filter_pairs) j->filter_pairs = ctx->alloc((size_t)SA_SLOTS * SA_MAX_OUT_ROWS * sizeof(uint2));
 }
+// The key columns of `right` for the async kernels; false = the synchronous operator takes the batch.  Without
+// sqlrs_hash_join_set_async_keys: ONE exactly compared INPUT_REF key of int32 / int64 / float64 without a NULL in the batch.  With
+// it (the header's rule): 1 .. 4 INPUT_REF keys of int32 / int64 / float64 / Utf8 (Utf8: the Utf8 switch as well), NULLs allowed;
+// kd->loader = the batch needs sa_probe_key (a NULL key in exact mode, any batch in hash mode).  A batch whose keys the
+// synchronous operator refuses (exact on one side only, another exact dtype) stays with it: it raises what there is to raise.
+struct SaKeyDesc {
+  int key_col = 0, key_is32 = 0, nkeys = 0;
+  uint32_t key_cols = 0;
+  bool loader = false;
+};
+static bool sa_probe_keys(sqlrs_hash_join *j, const sqlrs_batch_t *right, SaKeyDesc *kd) {
+  const size_t nk = j->rkeys.size();
+  if (j->comp.on || !right || nk < 1 || nk != j->lkeys.size() || right->num_columns > SA_MAX_COLS) return false;
+  if (!j->async_keys && (!j->exact || nk != 1)) return false;
+  if (nk > 4 || (j->exact && nk != 1)) return false;
+  bool any_null = false;
+  for (size_t k = 0; k < nk; k++) {
+    const Expr &e = j->rkeys[k];
+    if (e.nodes.size() != 1 || e.nodes[0].op != SQLRS_EXPR_INPUT_REF) return false;
+    const int kc = e.nodes[0].index;
+    if (kc < 0 || kc >= right->num_columns) return false;
+    const sqlrs_column_t &kcol = right->columns[kc];
+    const bool fixed = kcol.dtype == SQLRS_INT64 || kcol.dtype == SQLRS_FLOAT64 || kcol.dtype == SQLRS_INT32;
+    if (j->exact ? (!fixed || kcol.dtype != j->key_dtype) : !(fixed || (kcol.dtype == SQLRS_UTF8 && j->async_utf8))) return false;
+    if (!j->exact && nk == 1 && fixed) return false; // (one fixed-width probe key against a hashed build key: the operator's error)
+    any_null |= kcol.validity && kcol.null_count != 0;
+    kd->key_cols |= (uint32_t)kc << (8 * k);
+    if (k == 0) {
+      kd->key_col = kc;
+      kd->key_is32 = kcol.dtype == SQLRS_INT32;
+    }
+  }
+  if (j->exact && any_null && !j->async_keys) return false; // (NULL probe keys match NULL build keys: the key loader)
+  kd->nkeys = j->exact ? 0 : (int)nk;
+  kd->loader = !j->exact || any_null;
+  return true;
+}
 // true = the kernel above was queued for `right` and *t describes its slot
 static bool sa_probe_try(sqlrs_hash_join *j, const sqlrs_batch_t *right, sqlrs_ticket *t) {
   Ctx *ctx = j->ctx;
   const char *off_e = hook("SQLRS_ASYNC_FAST"); // test hook, read per call: 0 = every batch through the synchronous operator
   if (off_e && off_e[0] == '0') return false;
-  if (j->join_type != SQLRS_JOIN_INNER || !j->exact || j->comp.on || j->lkeys.size() != 1 || j->rkeys[0].nodes.size() != 1 ||
-      j->rkeys[0].nodes[0].op != SQLRS_EXPR_INPUT_REF || !right)
-    return false;
+  SaKeyDesc kd;
+  if (j->join_type != SQLRS_JOIN_INNER || !sa_probe_keys(j, right, &kd)) return false;
   const bool filt = sa_probe_filter_ready(j, right);
   if (j->has_filter && !filt) return false;
-  const int kc = j->rkeys[0].nodes[0].index;
-  if (kc < 0 || kc >= right->num_columns) return false;
-  const sqlrs_column_t &kcol = right->columns[kc];
-  if (kcol.dtype != j->key_dtype || (kcol.validity && kcol.null_count != 0)) return false; // (NULL probe keys: the general route)
-  if (kcol.dtype != SQLRS_INT64 && kcol.dtype != SQLRS_FLOAT64 && kcol.dtype != SQLRS_INT32) return false;
   const int nleft = (int)j->left.cols.size();
   if (nleft + right->num_columns > SA_MAX_COLS) return false;
   int32_t ldt[SA_MAX_COLS];
@@ -1527,14 +1599,16 @@ static bool sa_probe_try(sqlrs_hash_join *j, const sqlrs_batch_t *right, sqlrs_t
   SaRing *r = sa_ring(ctx);
   const int slot = r ? sa_take_slot(r) : -1;
   if (slot < 0) return false;
-  SaProbeUtf8Params p;
+  SaWithKeys<SaProbeUtf8Params> p;
   if (!sa_stage_input(right, r->in_area(slot), &p.lay, nleft, ldt, utf8, SA_NONE, utf8 ? front_bytes : nullptr)) { // (the byte bound: checked before anything is written)
     r->busy[slot] = false;
     return false;
   }
   p.nleft = nleft;
-  p.key_col = kc;
-  p.key_is32 = kcol.dtype == SQLRS_INT32;
+  p.key_col = kd.key_col;
+  p.key_is32 = kd.key_is32;
+  p.nkeys = kd.nkeys;
+  p.key_cols = kd.key_cols;
   p.dense = j->dense ? 1 : 0;
   for (int c = 0; c < SA_MAX_COLS; c++) {
     p.lvals[c] = c < nleft ? j->left.cols[(size_t)c].values : nullptr;
@@ -1552,9 +1626,11 @@ static bool sa_probe_try(sqlrs_hash_join *j, const sqlrs_batch_t *right, sqlrs_t
     j->async_ordered = true;
   }
   const SaProgram *prog = filt ? j->filter_prog->as<SaProgram>() : nullptr;
-  if (filt && utf8) sa_enqueue(ctx, r, j, sa_probe_launch<true, true>, SaWithFilter<SaProbeUtf8Params>(p, prog), slot);
+  if (filt && kd.loader) sa_enqueue(ctx, r, j, sa_probe_launch<true, true, true>, SaWithFilter<SaWithKeys<SaProbeUtf8Params>>(p, prog), slot);
+  else if (kd.loader) sa_enqueue(ctx, r, j, sa_probe_launch<true, false, true>, p, slot);
+  else if (filt && utf8) sa_enqueue(ctx, r, j, sa_probe_launch<true, true>, SaWithFilter<SaProbeUtf8Params>(p, prog), slot);
   else if (filt) sa_enqueue(ctx, r, j, sa_probe_launch<false, true>, SaWithFilter<SaProbeParams>(p, prog), slot);
-  else if (utf8) sa_enqueue(ctx, r, j, sa_probe_launch<true>, p, slot);
+  else if (utf8) sa_enqueue(ctx, r, j, sa_probe_launch<true>, (const SaProbeUtf8Params &)p, slot);
   else sa_enqueue(ctx, r, j, sa_probe_launch<false>, (const SaProbeParams &)p, slot);
   t->slot = slot;
   t->seq = p.seq;
@@ -1616,10 +1692,12 @@ template <class Base> struct SaGenWithFilter : Base {
   SaGenWithFilter() = default;
   SaGenWithFilter(const Base &b, const SaProgram *pr, uint2 *pl) : Base(b), prog(pr), pairs(pl) {}
 };
-template <bool UTF8, bool FILTER> using SaProbeGenP =
-    std::conditional_t<FILTER, SaGenWithFilter<std::conditional_t<UTF8, SaProbeGenUtf8Params, SaProbeGenParams>>, std::conditional_t<UTF8, SaProbeGenUtf8Params, SaProbeGenParams>>;
-template <bool UTF8, bool FILTER>
-__global__ __launch_bounds__(1024) void sa_probe_general_kernel(SaGroup<SaProbeGenP<UTF8, FILTER>> grp) {
+// sqlrs_hash_join_set_async_keys (KEYS = true): sa_probe_key, as in sa_probe_kernel
+template <bool UTF8, bool FILTER, bool KEYS> using SaProbeGenBaseP = std::conditional_t<KEYS, SaWithKeys<SaProbeGenUtf8Params>, std::conditional_t<UTF8, SaProbeGenUtf8Params, SaProbeGenParams>>;
+template <bool UTF8, bool FILTER, bool KEYS = false> using SaProbeGenP = std::conditional_t<FILTER, SaGenWithFilter<SaProbeGenBaseP<UTF8, FILTER, KEYS>>, SaProbeGenBaseP<UTF8, FILTER, KEYS>>;
+template <bool UTF8, bool FILTER, bool KEYS = false>
+__global__ __launch_bounds__(1024) void sa_probe_general_kernel(SaGroup<SaProbeGenP<UTF8, FILTER, KEYS>> grp) {
+  static_assert(!KEYS || UTF8, "the key loader is instantiated with the Utf8 kernels only");
   const auto &p = grp.p[blockIdx.x]; // (one workgroup per batch of the group)
   __shared__ uint32_t s_off[SA_MAX_ROWS], s_start[SA_MAX_ROWS]; // per probe row: first output row; run start / build row / DENSE_EMPTY
   __shared__ uint32_t s_w[16], s_nulls[SA_MAX_COLS], s_err;
@@ -1638,22 +1716,26 @@ __global__ __launch_bounds__(1024) void sa_probe_general_kernel(SaGroup<SaProbeG
     if (threadIdx.x == 0) s_div0 = 0;
   }
   const uint32_t rows = p.lay.rows;
-  const SaCol &kc = p.lay.c[p.nleft + p.key_col];
+  const SaCol &kc = p.lay.c[p.nleft + p.key_col]; // (the first key column)
   uint32_t base = 0;
   for (uint32_t t = 0; t * 1024u < rows; t++) { // (uniform)
     const uint32_t r = t * 1024u + threadIdx.x;
     uint32_t e = 0, start = DENSE_EMPTY;
     if (r < rows) {
-      const uint64_t key = p.key_is32 ? (uint64_t)(int64_t)((const int32_t *)(p.in + kc.in_off))[r] : ((const uint64_t *)(p.in + kc.in_off))[r];
+      bool is_null;
+      const uint64_t key = sa_probe_key<KEYS>(p, kc, r, &is_null);
       uint32_t cnt = 0;
       if (p.mode == 0) {
         const uint64_t d = key - p.dt.kmin;
-        start = dense_get(p.dt, d < p.dt.range ? d : p.dt.range + 1);
+        if (KEYS && is_null) start = p.dt.null_head;
+        else start = dense_get(p.dt, d < p.dt.range ? d : p.dt.range + 1);
         cnt = start != DENSE_EMPTY;
       } else if (p.mode == 1) {
-        const Slot sl = probe_slot(p.table, p.mask, key, false);
+        const Slot sl = probe_slot(p.table, p.mask, key, KEYS && is_null);
         start = sl.head;
         cnt = sl.count;
+      } else if (KEYS && is_null) { // (dd_table is only built without a NULL build key: no partner)
+        cnt = 0;
       } else {
         const uint64_t d = key - p.dup_min;
         const uint32_t *en = p.dd + (d < p.dup_range ? d : p.dup_range + 1); // (a key outside the range reads the empty run behind it)
@@ -1704,7 +1786,7 @@ __global__ __launch_bounds__(1024) void sa_probe_general_kernel(SaGroup<SaProbeG
         const uint32_t st = s_start[r];
         if (st != DENSE_EMPTY) brow = p.unique ? st : p.rows_by_slot[st + (o - s_off[r])];
         bool valid, div0 = false;
-        const unsigned long long v = sa_eval_row(prog, SaJoinedLoad<SaProbeGenP<UTF8, FILTER>>{p, r, brow}, &valid, &div0);
+        const unsigned long long v = sa_eval_row(prog, SaJoinedLoad<SaProbeGenP<UTF8, FILTER, KEYS>>{p, r, brow}, &valid, &div0);
         if (div0) s_div0 = 1u;
         keep = valid && v != 0;
       }
@@ -1855,11 +1937,12 @@ __global__ __launch_bounds__(1024) void sa_probe_general_kernel(SaGroup<SaProbeG
     if (threadIdx.x == 0 && s_div0 && !s_err) s_err = 1; // (thread 0 reads both behind phase A's last barrier; sa_publish reads s_err behind its own)
   sa_publish((SaHeader *)p.out, p.seq, total, s_nulls, p.lay.ncols, &s_err);
 }
-template <bool UTF8, bool FILTER = false> static void sa_probe_general_launch(SaRing *r, Ctx *ctx) {
-  using P = SaProbeGenP<UTF8, FILTER>;
+template <bool UTF8, bool FILTER = false, bool KEYS = false> static void sa_probe_general_launch(SaRing *r, Ctx *ctx) {
+  using P = SaProbeGenP<UTF8, FILTER, KEYS>;
+  static_assert(sizeof(P) <= SA_PARAM_MAX, "parameter block too large");
   SaGroup<P> g;
   for (int i = 0; i < r->pend_n; i++) std::memcpy(&g.p[i], r->pend_buf + (size_t)i * SA_PARAM_MAX, sizeof(P));
-  sa_probe_general_kernel<UTF8, FILTER><<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g);
+  sa_probe_general_kernel<UTF8, FILTER, KEYS><<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g);
   SQ_HIP(hipGetLastError());
 }
 // M: the most build rows that share one key — the largest Slot.count of the 16-byte-slot table (its NULL-key slot included) or
@@ -1893,16 +1976,10 @@ static bool sa_probe_general_try(sqlrs_hash_join *j, const sqlrs_batch_t *right,
   if (!j->async_general) return false;
   const char *off_e = hook("SQLRS_ASYNC_FAST"); // test hook, read per call: 0 = every batch through the synchronous operator
   if (off_e && off_e[0] == '0') return false;
-  if (!j->exact || j->comp.on || j->lkeys.size() != 1 || j->rkeys[0].nodes.size() != 1 ||
-      j->rkeys[0].nodes[0].op != SQLRS_EXPR_INPUT_REF || !right || right->num_rows < 0 || right->num_rows > (int64_t)SA_MAX_ROWS)
-    return false;
+  SaKeyDesc kd;
+  if (!right || right->num_rows < 0 || right->num_rows > (int64_t)SA_MAX_ROWS || !sa_probe_keys(j, right, &kd)) return false;
   const bool filt = sa_probe_filter_ready(j, right);
   if (j->has_filter && !filt) return false;
-  const int kc = j->rkeys[0].nodes[0].index;
-  if (kc < 0 || kc >= right->num_columns) return false;
-  const sqlrs_column_t &kcol = right->columns[kc];
-  if (kcol.dtype != j->key_dtype || (kcol.validity && kcol.null_count != 0)) return false; // (NULL probe keys match NULL build keys: the general route)
-  if (kcol.dtype != SQLRS_INT64 && kcol.dtype != SQLRS_FLOAT64 && kcol.dtype != SQLRS_INT32) return false;
   const int nleft = (int)j->left.cols.size();
   if (nleft + right->num_columns > SA_MAX_COLS) return false;
   int32_t ldt[SA_MAX_COLS];
@@ -1923,14 +2000,16 @@ static bool sa_probe_general_try(sqlrs_hash_join *j, const sqlrs_batch_t *right,
   SaRing *r = sa_ring(ctx);
   const int slot = r ? sa_take_slot(r) : -1;
   if (slot < 0) return false;
-  SaProbeGenUtf8Params p;
+  SaWithKeys<SaProbeGenUtf8Params> p;
   if (!sa_stage_input(right, r->in_area(slot), &p.lay, nleft, ldt, utf8, (uint32_t)out_rows, utf8 ? front_bytes : nullptr)) { // (the byte bound: checked before anything is written)
     r->busy[slot] = false;
     return false;
   }
   p.nleft = nleft;
-  p.key_col = kc;
-  p.key_is32 = kcol.dtype == SQLRS_INT32;
+  p.key_col = kd.key_col;
+  p.key_is32 = kd.key_is32;
+  p.nkeys = kd.nkeys;
+  p.key_cols = kd.key_cols;
   p.mode = mode;
   p.unique = j->unique ? 1 : 0;
   p.outer_right = (j->join_type == SQLRS_JOIN_RIGHT || j->join_type == SQLRS_JOIN_FULL) ? 1 : 0;
@@ -1958,9 +2037,11 @@ static bool sa_probe_general_try(sqlrs_hash_join *j, const sqlrs_batch_t *right,
   }
   const SaProgram *prog = filt ? j->filter_prog->as<SaProgram>() : nullptr;
   uint2 *pairs = filt ? j->filter_pairs->as<uint2>() + (size_t)slot * SA_MAX_OUT_ROWS : nullptr; // (a slot is reused only after its ticket was waited for)
-  if (filt && utf8) sa_enqueue(ctx, r, j, sa_probe_general_launch<true, true>, SaGenWithFilter<SaProbeGenUtf8Params>(p, prog, pairs), slot);
+  if (filt && kd.loader) sa_enqueue(ctx, r, j, sa_probe_general_launch<true, true, true>, SaGenWithFilter<SaWithKeys<SaProbeGenUtf8Params>>(p, prog, pairs), slot);
+  else if (kd.loader) sa_enqueue(ctx, r, j, sa_probe_general_launch<true, false, true>, p, slot);
+  else if (filt && utf8) sa_enqueue(ctx, r, j, sa_probe_general_launch<true, true>, SaGenWithFilter<SaProbeGenUtf8Params>(p, prog, pairs), slot);
   else if (filt) sa_enqueue(ctx, r, j, sa_probe_general_launch<false, true>, SaGenWithFilter<SaProbeGenParams>(p, prog, pairs), slot);
-  else if (utf8) sa_enqueue(ctx, r, j, sa_probe_general_launch<true>, p, slot);
+  else if (utf8) sa_enqueue(ctx, r, j, sa_probe_general_launch<true>, (const SaProbeGenUtf8Params &)p, slot);
   else sa_enqueue(ctx, r, j, sa_probe_general_launch<false>, (const SaProbeGenParams &)p, slot);
   t->slot = slot;
   t->seq = p.seq;
@@ -2005,6 +2086,15 @@ int sqlrs_hash_join_set_async_filter(sqlrs_hash_join_t *j, int on) {
   return guard(j->ctx, [&] {
     if (j->probe_started) fail(SQLRS_ERR_INTERNAL, "sqlrs_hash_join_set_async_filter: after the first probe call");
     j->async_filter = on != 0;
+  });
+}
+// the switch of the key loader in both async probe kernels (NULL probe keys, Utf8 keys, 2 .. 4 key columns): before the first
+// probe call of any kind
+int sqlrs_hash_join_set_async_keys(sqlrs_hash_join_t *j, int on) {
+  if (!j) return SQLRS_ERR_INTERNAL;
+  return guard(j->ctx, [&] {
+    if (j->probe_started) fail(SQLRS_ERR_INTERNAL, "sqlrs_hash_join_set_async_keys: after the first probe call");
+    j->async_keys = on != 0;
   });
 }
 // the switch of the Utf8 payload columns in both async probe kernels: before the first probe call of any kind

@@ -105,6 +105,9 @@ struct sqlrs_hash_join {
   int filter_prog_state = 0;
   std::vector<unsigned char> filter_prog_host;
   sq::BufP filter_prog, filter_pairs;
+  // sqlrs_hash_join_set_async_keys: both async probe kernels load the key of a probe row themselves (sa_probe_key, join.hip): NULL
+  // probe keys in exact mode, and the hashed key of a Utf8 key or of 2 .. 4 key columns (key_hash.hpp)
+  bool async_keys = false;
 };
 
 // builds the deferred hash table of a `lazy_table` join (join.hip); no-op otherwise

@@ -7,6 +7,7 @@
 //    mixer instead of ahash (hash values are never observable in operator output).
 #include "common.hpp"
 #include "device_utils.hpp"
+#include "key_hash.hpp"
 #include "prims.hpp"
 
 namespace sq {
@@ -22,28 +23,21 @@ __global__ void widen_bool_kernel(const uint64_t *__restrict__ in, int64_t n,
   if (i < n) out[i] = (in[i >> 6] >> (i & 63)) & 1;
 }
 
-__device__ __forceinline__ uint64_t combine_hashes(uint64_t l, uint64_t r) { // hash_utils.rs:13-16
-  uint64_t h = (uint64_t)(17 * 37) + l;
-  return h * 37 + r;
-}
-
-// folds one column into the running per-row hash (hash stays put on NULL)
+// folds one column into the running per-row hash (hash stays put on NULL); the arithmetic is key_hash.hpp's
 template <class T>
 __global__ void fold_fixed_kernel(const T *__restrict__ in, const uint64_t *__restrict__ validity,
                                   int64_t n, uint64_t tag, int multi, uint64_t *__restrict__ h) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
   if (validity && !((validity[i >> 6] >> (i & 63)) & 1)) return;
-  uint64_t v = mix64((uint64_t)in[i] + tag);
-  h[i] = multi ? combine_hashes(v, h[i]) : v;
+  h[i] = key_fold(key_hash_fixed((uint64_t)in[i], tag), h[i], multi);
 }
 __global__ void fold_bool_kernel(const uint64_t *__restrict__ in, const uint64_t *__restrict__ validity,
                                  int64_t n, int multi, uint64_t *__restrict__ h) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
   if (validity && !((validity[i >> 6] >> (i & 63)) & 1)) return;
-  uint64_t v = mix64(((in[i >> 6] >> (i & 63)) & 1) ^ 0x0808080808080808ULL);
-  h[i] = multi ? combine_hashes(v, h[i]) : v;
+  h[i] = key_fold(key_hash_bool((in[i >> 6] >> (i & 63)) & 1), h[i], multi);
 }
 __global__ void fold_utf8_kernel(const uint8_t *__restrict__ data, const int32_t *__restrict__ off,
                                  const uint64_t *__restrict__ validity, int64_t n, int multi,
@@ -51,13 +45,7 @@ __global__ void fold_utf8_kernel(const uint8_t *__restrict__ data, const int32_t
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
   if (validity && !((validity[i >> 6] >> (i & 63)) & 1)) return;
-  uint64_t x = 0xcbf29ce484222325ULL; // FNV-1a over the bytes, then the mixer
-  for (int32_t k = off[i]; k < off[i + 1]; k++) {
-    x ^= data[k];
-    x *= 0x100000001b3ULL;
-  }
-  uint64_t v = mix64(x ^ 0x7575757575757575ULL);
-  h[i] = multi ? combine_hashes(v, h[i]) : v;
+  h[i] = key_fold(key_hash_utf8(data, off[i], off[i + 1]), h[i], multi); // FNV-1a over the bytes, then the mixer
 }
 
 // Several fixed-width key columns folded in ONE pass (round 6): the column-by-column form above reads and rewrites the running
@@ -79,7 +67,7 @@ __global__ __launch_bounds__(256) void fold_fixed_multi_kernel(FoldCols fc, int6
       if (c >= fc.n) break;
       if (fc.valid[c] && !((fc.valid[c][i >> 6] >> (i & 63)) & 1)) continue;
       const uint64_t x = fc.is32[c] ? (uint64_t)((const uint32_t *)fc.v[c])[i] : ((const uint64_t *)fc.v[c])[i];
-      acc = combine_hashes(mix64(x + fc.tag[c]), acc);
+      acc = combine_hashes(key_hash_fixed(x, fc.tag[c]), acc);
     }
     h[i] = acc;
   }
@@ -102,16 +90,9 @@ __global__ void fold_strong_kernel(const void *__restrict__ data, const int32_t 
   else if (MODE == 1)
     v = mix64((uint64_t)((const uint32_t *)data)[i] ^ 0x3232323200000000ULL);
   else if (MODE == 2)
-    v = mix64(((((const uint64_t *)data)[i >> 6] >> (i & 63)) & 1) ^ 0x0808080808080808ULL);
-  else {
-    uint64_t x = 0xcbf29ce484222325ULL;
-    const uint8_t *b = (const uint8_t *)data;
-    for (int32_t k = off[i]; k < off[i + 1]; k++) {
-      x ^= b[k];
-      x *= 0x100000001b3ULL;
-    }
-    v = mix64(x ^ 0x7575757575757575ULL);
-  }
+    v = key_hash_bool((((const uint64_t *)data)[i >> 6] >> (i & 63)) & 1);
+  else
+    v = key_hash_utf8((const uint8_t *)data, off[i], off[i + 1]);
   h[i] = mix64((h[i] ^ salt) * 0x9e3779b97f4a7c15ULL + v);
 }
 
@@ -214,7 +195,7 @@ NKeys normalize_keys(Ctx *ctx, const std::vector<DCol> &cols_in, int64_t rows) {
       fc.v[c] = col.values;
       fc.valid[c] = (col.validity && col.null_count != 0) ? col.validity : nullptr;
       fc.is32[c] = col.dtype == SQLRS_INT32;
-      fc.tag[c] = col.dtype == SQLRS_INT32 ? 0x3232323200000000ULL : 0x9e3779b97f4a7c15ULL;
+      fc.tag[c] = col.dtype == SQLRS_INT32 ? KEY_TAG_32 : KEY_TAG_64;
     }
     if (ok) {
       const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(rows, 256 * 4), 16 * (int64_t)ctx->num_cus));
@@ -232,12 +213,12 @@ NKeys normalize_keys(Ctx *ctx, const std::vector<DCol> &cols_in, int64_t rows) {
     switch (c.dtype) {
     case SQLRS_INT32:
       fold_fixed_kernel<uint32_t><<<g, b, 0, ctx->stream>>>(c.v<uint32_t>(), v, rows,
-                                                            0x3232323200000000ULL, multi, h);
+                                                            KEY_TAG_32, multi, h);
       break;
     case SQLRS_INT64:
     case SQLRS_FLOAT64:
       fold_fixed_kernel<uint64_t><<<g, b, 0, ctx->stream>>>(c.v<uint64_t>(), v, rows,
-                                                            0x9e3779b97f4a7c15ULL, multi, h);
+                                                            KEY_TAG_64, multi, h);
       break;
     case SQLRS_BOOLEAN:
       fold_bool_kernel<<<g, b, 0, ctx->stream>>>(c.v<uint64_t>(), v, rows, multi, h);

@@ -14,7 +14,7 @@
 //     back to a stream synchronisation when it does not show up, and copies the rows into an ordinary HOST batch.
 // Anything the fast path does not take — predicates that read a Boolean / Utf8 column (unless the operator's all-types switch is
 // on, last paragraph but one), a batch that carries a Boolean column (the same switch), predicates of more than 24 nodes, Utf8
-// columns around a join (unless the join's Utf8 switch is on, below), more than 4096 rows, DEVICE input, join filters (unless the join's filter switch is on, last paragraph), NULL probe keys, composite or hash-only join keys,
+// columns around a join (unless the join's Utf8 switch is on, below), more than 4096 rows, DEVICE input, join filters (unless the join's filter switch is on, below), NULL probe keys and Utf8 / multi-column join keys (unless the join's key switch is on, below), Boolean keys, the opt-in composite key,
 // duplicate build keys and outer joins (unless the join's switch is on, next paragraph) — runs the synchronous operator
 // inside push_async and parks the finished batch in the ticket: same results, same one-output-per-input rule, no speed-up.
 // sqlrs_hash_join_set_async_general(j, 1): Left / Right / Full joins and build sides with duplicate keys take ONE launch per
@@ -34,6 +34,9 @@
 // evaluates it per candidate, compacts the kept candidates into a list in HBM (a region per ring slot), appends the Right / Full
 // probe rows that kept none, and emits from the list — apply_join_filter's order and its visited marks; a valid candidate that
 // divides by zero is SaHeader::pad = 1, the evaluator's error at the wait.  The output bound is the unfiltered one (candidates).
+// sqlrs_hash_join_set_async_keys(j, 1): both probe kernels load the key of a probe row themselves (the KEYS instantiations, sa_probe_key,
+// join.hip): a NULL key of an exactly compared key takes the NULL build rows, a Utf8 key or a key of 2 - 4 columns is the u64 that
+// normalize_keys computes (key_hash.hpp: one definition for the fold_* kernels and the loader), looked up as a value: match-by-hash.
 // sqlrs_filter_set_async_all_types(f, 1) / sqlrs_project_set_async_all_types(p, 1): the program also reads Utf8 and Boolean columns
 // (sa_compile with `wide`, sa_eval_row<true>, SaSlotLoadWide: the `wide` instantiations of sa_filter_kernel / sa_project_kernel, chosen
 // per batch — a batch with nothing wide in it keeps the narrow kernel).  A Utf8 value is ONE stack word {length, byte offset in the slot's

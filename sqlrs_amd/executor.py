@@ -147,7 +147,8 @@ class HashJoinExecutor:
     def __init__(self, backend: abi.Backend, left_child: Iterable, right_child: Iterable,
                  join_type: str, join_condition: JoinCondition, join_output_schema: pa.Schema,
                  num_left_columns: int, out_mem: int = abi.MEM_HOST, many: int = 0, depth: int = 0,
-                 async_general: bool = False, async_utf8: bool = False, async_filter: bool = False):
+                 async_general: bool = False, async_utf8: bool = False, async_filter: bool = False,
+                 async_keys: bool = False):
         self.backend = backend
         self.depth = depth  # > 0: probe batches through sqlrs_hash_join_probe_push_async, that many tickets in flight
         # sqlrs_hash_join_set_async_general: with depth > 0, outer joins and duplicate build keys take one launch per batch too
@@ -159,6 +160,9 @@ class HashJoinExecutor:
         # sqlrs_hash_join_set_async_filter: with depth > 0, a join WITH a join filter takes the one-launch kernels too, the filter
         # evaluated inside them (again: a backend without the entry point runs unchanged)
         self.async_filter = async_filter
+        # sqlrs_hash_join_set_async_keys: with depth > 0, batches with NULL probe keys, a Utf8 key (with async_utf8) or 2 to 4 key
+        # columns take the one-launch kernels too (again: a backend without the entry point runs unchanged)
+        self.async_keys = async_keys
         # many > 1: that many probe batches go to sqlrs_hash_join_probe_push_many together (same stream of joined batches)
         self.many = many
         self.left_child, self.right_child = left_child, right_child
@@ -185,7 +189,7 @@ class HashJoinExecutor:
             be.ctx, JoinType[self.join_type.lower()], len(self.join_condition.on), lk, rk, filt,
             len(right_fields), rd, C.byref(h)))
         for flag, name in ((self.async_general, "hash_join_set_async_general"), (self.async_utf8, "hash_join_set_async_utf8"),
-                           (self.async_filter, "hash_join_set_async_filter")):
+                           (self.async_filter, "hash_join_set_async_filter"), (self.async_keys, "hash_join_set_async_keys")):
             setter = getattr(be.lib, be.prefix + name, None)
             if flag and setter is not None:
                 st = setter(h, 1)
