@@ -198,6 +198,33 @@ struct Ctx {
     JR_COUNT_
   };
   int64_t join_route[JR_COUNT_] = {};
+  // Which route of ORDER BY ran (counts, reported like agg_route under ORDER_ROUTE_NAMES, ctx.hip, behind the join's entries;
+  // incremented on the host where the decision is taken, ops.hip / order_fast.hip — DESIGN.md "Route witnesses of ORDER BY").
+  // One sort — an outer sqlrs_order_finish, or the inner Order of the top-k candidates / of the NULL split's valid rows —
+  // moves exactly one of GENERAL / NARROW / WIDE / IN_ORDER, unless top-k or the NULL split handed it to an inner sort (which
+  // then moves its own).  One attempt that launched split passes moves exactly one of LOOKBACK / COUNTING.
+  enum OrderRoute {
+    OR_GENERAL,        // the LSD path of sqlrs_order_finish sorted the rows (any row count, 0 included)
+    OR_UTF8,           // ... and sorted a Utf8 key with sort_perm_by_utf8 (once per Utf8 key)
+    OR_NARROW,         // order_fast_impl produced the result (<= 32 varying key bits)
+    OR_NARROW_HBM_ONLY, // its second try with every key bit through HBM passes ran (a group beyond FIN_CAP)
+    OR_LOOKBACK, OR_COUNTING, // an attempt's (first) split pass chained over its tiles, or counted and scanned
+    OR_REC12, OR_REC16, // an attempt moved 12-byte {key offset, value} / 16-byte {word, value} records between or out of its passes
+    OR_WIDE,           // order_wide produced the result (splitters)
+    OR_WIDE_DECLINED,  // order_wide was entered and declined: n < G * samples, or a mixed group beyond FIN_CAP
+    OR_WIDE_PURE,      // ... copied groups of one value with owk_pure_copy_kernel (pure_chunks > 0)
+    OR_WIDE_FIN2, OR_WIDE_FIN3, // ... launched the finish for groups beyond 8 * FIN_WG / beyond 16 * FIN_WG rows
+    OR_HEAVY_TO_WIDE,  // the heavy-value probe sent a column of <= 32 varying bits to order_wide
+    OR_SAMPLED, OR_SAMPLE_MISSED, // order_fast took the key range from a sample / a key lay outside it: the exact retry ran
+    OR_IN_ORDER,       // the input was returned as it came
+    OR_COMPOSITE, OR_COMPOSITE_NULLABLE, // order_composite produced the result / ... and a key had NULLs (a valid bit)
+    OR_COMPOSITE_TOO_WIDE, // order_composite declined: the fields need more than 64 bits
+    OR_NULL_SPLIT,     // order_null_split produced the result (the valid rows through an inner Order)
+    OR_TOPK, OR_TOPK_IGNORED, // order_topk produced the candidates / ran and found fewer than the limit: hint ignored
+    OR_ALLOC_DECLINED, // a fast attempt ran out of pool memory and was treated as "route not taken"
+    OR_COUNT_
+  };
+  int64_t order_route[OR_COUNT_] = {};
   std::shared_ptr<void> small_ring; // the pinned ring of the single-batch async path (small_async.hpp), created on first use
   void sync() { SQ_HIP(hipStreamSynchronize(stream)); }
   // copies `bytes` from device to the pinned area and synchronises; returns host pointer

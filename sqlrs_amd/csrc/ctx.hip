@@ -1289,6 +1289,22 @@ int sqlrs_ctx_profile_read(sqlrs_ctx_t *ctx, int cap, const char **names, double
     }
     n++;
   }
+  // (counts: which route of ORDER BY ran — common.hpp: Ctx::OrderRoute, in that order; behind every older entry)
+  static const char *const ORDER_ROUTE_NAMES[Ctx::OR_COUNT_] = {
+      "order_general", "order_utf8_key", "order_narrow", "order_narrow_hbm_only", "order_form_lookback", "order_form_counting",
+      "order_rec12", "order_rec16", "order_wide", "order_wide_declined", "order_wide_pure_copy", "order_wide_finish2",
+      "order_wide_finish3", "order_heavy_to_wide", "order_range_sampled", "order_range_missed", "order_in_order",
+      "order_composite", "order_composite_nullable", "order_composite_too_wide", "order_null_split", "order_topk",
+      "order_topk_ignored", "order_alloc_declined"};
+  for (int r = 0; r < Ctx::OR_COUNT_; r++) {
+    if (!ctx->order_route[r]) continue;
+    if (n < cap) {
+      names[n] = ORDER_ROUTE_NAMES[r];
+      total_ms[n] = 0;
+      launches[n] = ctx->order_route[r];
+    }
+    n++;
+  }
   return n;
 }
 

@@ -766,6 +766,7 @@ static bool order_topk(sqlrs_order *o, DBatch &all, int kc, int out_mem, sqlrs_b
       o->topk_candidates = kept->num_rows;
       done = true;
     }
+    ctx->order_route[done ? Ctx::OR_TOPK : Ctx::OR_TOPK_IGNORED]++;
   } catch (...) {
     cleanup();
     throw;
@@ -851,6 +852,7 @@ static bool order_null_split(sqlrs_order *o, DBatch &all, int kc, int out_mem, s
     throw;
   }
   cleanup();
+  ctx->order_route[Ctx::OR_NULL_SPLIT]++;
   return true;
 }
 
@@ -985,6 +987,7 @@ int sqlrs_order_finish(sqlrs_order_t *o, int out_mem, sqlrs_batch_t **out) {
         } catch (const Error &e) {
           if (e.status != SQLRS_ERR_DEVICE || e.msg.rfind("hipMalloc(", 0) != 0) throw;
           (void)hipGetLastError(); // (clears the sticky out-of-memory error code)
+          ctx->order_route[Ctx::OR_ALLOC_DECLINED]++;
           ko = DCol();
           co = DCol();
           fperm = nullptr;
@@ -1038,6 +1041,7 @@ int sqlrs_order_finish(sqlrs_order_t *o, int out_mem, sqlrs_batch_t **out) {
         } catch (const Error &e) { // (an allocation failure of the attempt is "route not taken", as above)
           if (e.status != SQLRS_ERR_DEVICE || e.msg.rfind("hipMalloc(", 0) != 0) throw;
           (void)hipGetLastError();
+          ctx->order_route[Ctx::OR_ALLOC_DECLINED]++;
           kout.clear();
           co = DCol();
           fperm = nullptr;
@@ -1077,6 +1081,7 @@ int sqlrs_order_finish(sqlrs_order_t *o, int out_mem, sqlrs_batch_t **out) {
         if (plain && kcol.validity && kcol.null_count != 0 && order_null_split(o, all, kc, out_mem, out)) return;
       }
     }
+    ctx->order_route[Ctx::OR_GENERAL]++; // (route witness, common.hpp Ctx::OrderRoute: nothing above took the rows)
     BufP perm = ctx->alloc(4 * (size_t)n1), keys = ctx->alloc(8 * (size_t)n1);
     iota_u32(ctx, perm->as<uint32_t>(), n);
     dim3 g((unsigned)ceil_div(n1, 256)), b(256);
@@ -1110,6 +1115,7 @@ int sqlrs_order_finish(sqlrs_order_t *o, int out_mem, sqlrs_batch_t **out) {
         sort_key_kernel<3><<<g, b, 0, ctx->stream>>>(c.values, valid, perm->as<uint32_t>(), n, desc, keys->as<uint64_t>());
         break;
       case SQLRS_UTF8: {
+        ctx->order_route[Ctx::OR_UTF8]++;
         sort_perm_by_utf8(ctx, c, valid, desc, perm->as<uint32_t>(), keys->as<uint64_t>(), n);
         bits = 0; // sorted above
         break;

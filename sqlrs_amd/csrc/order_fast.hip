@@ -46,7 +46,10 @@ static bool order_wide(Ctx *ctx, const DCol &key, int desc, const DCol *carry, i
   int per_group = OWK_SAMPLES;
   if (const char *e = hook("SQLRS_ORDER_SAMPLES")) per_group = std::max(1, std::min(256, std::atoi(e))); // (A/B hook, read per call)
   const int64_t S = (int64_t)G * per_group;
-  if (n < S) return false;
+  if (n < S) {
+    ctx->order_route[Ctx::OR_WIDE_DECLINED]++;
+    return false;
+  }
   const int kb = range ? 64 - __builtin_clzll(range) : 1;
   const bool pay_rows = want_perm, has_pay = pay_rows || carry != nullptr;
   // 0. splitters
@@ -81,6 +84,9 @@ static bool order_wide(Ctx *ctx, const DCol &key, int desc, const DCol *carry, i
   const char *lb_e = hook("SQLRS_ORDER_LB"), *lbf_e = hook("SQLRS_ORDER_LB_TEST_FAIL");
   const bool lb1 = rec1 && n < (1ll << 30) && !g_order_lb_off.load() && !wide_lb_skip && !(lb_e && lb_e[0] == '0');
   BufP ghb1, lbdesc1;
+  // (route witnesses, common.hpp Ctx::OrderRoute: the form of this attempt)
+  ctx->order_route[lb1 ? Ctx::OR_LOOKBACK : Ctx::OR_COUNTING]++;
+  ctx->order_route[Ctx::OR_REC16] += has_pay;
   if (lb1) {
     ProfScope ps(ctx, "order_split");
     ghb1 = ctx->alloc(4 * 260);
@@ -160,7 +166,10 @@ static bool order_wide(Ctx *ctx, const DCol &key, int desc, const DCol *carry, i
     } skip;
     return order_wide<KIND>(ctx, key, desc, carry, n, imin, range, key_out, carry_out, perm_out, want_perm);
   }
-  if (max_group > FIN_CAP) return false; // thousands of distinct keys between two neighbouring samples: general path
+  if (max_group > FIN_CAP) { // thousands of distinct keys between two neighbouring samples: general path
+    ctx->order_route[Ctx::OR_WIDE_DECLINED]++;
+    return false;
+  }
   // 4. finish
   key_out->dtype = key.dtype;
   key_out->length = n;
@@ -218,6 +227,10 @@ static bool order_wide(Ctx *ctx, const DCol &key, int desc, const DCol *carry, i
     }
     SQ_HIP(hipGetLastError());
   }
+  ctx->order_route[Ctx::OR_WIDE]++;
+  ctx->order_route[Ctx::OR_WIDE_PURE] += pure_chunks > 0;
+  ctx->order_route[Ctx::OR_WIDE_FIN2] += max_group > 8 * FIN_WG;
+  ctx->order_route[Ctx::OR_WIDE_FIN3] += max_group > 16 * FIN_WG;
   return true;
 }
 
@@ -252,6 +265,7 @@ static bool order_fast_impl(Ctx *ctx, const DCol &key, int desc, const DCol *car
     order_inversion_kernel<KIND, false><<<dim3(blocks), dim3(256), 0, ctx->stream>>>(key.values, n, desc, inv);
     SQ_HIP(hipGetLastError());
     if (ctx->fetch_value(inv) == 0) {
+      ctx->order_route[Ctx::OR_IN_ORDER]++;
       *in_order = true; // the rows are in the requested order already: nothing to do
       return false;
     }
@@ -310,7 +324,9 @@ static bool order_fast_impl(Ctx *ctx, const DCol &key, int desc, const DCol *car
     // a value with a visible share of the rows: the splitter route gives it a group of its own that is copied, not sorted
     // (order_wide works on any range; if it declines, the plan below runs as before)
     // (only when low bits are left for the in-LDS finish: with every bit sorted in HBM no group is too large)
-    if (heavy_probe && rbits > 0 && heavy_cnt >= OW_HEAVY_MIN &&
+    const bool to_wide = heavy_probe && rbits > 0 && heavy_cnt >= OW_HEAVY_MIN;
+    ctx->order_route[Ctx::OR_HEAVY_TO_WIDE] += to_wide;
+    if (to_wide &&
         order_wide<KIND>(ctx, key, desc, carry, n, optimistic ? 0 : imin, optimistic ? ~0ull : range, key_out, carry_out, perm_out, want_perm))
       return true;
   }
@@ -418,6 +434,9 @@ static bool order_fast_impl(Ctx *ctx, const DCol &key, int desc, const DCol *car
   bool slim = false; // the look-back form moved 12-byte records (ow_scatter_kernel<.., SLIM>): the finish reads those
   unsigned int *lbw = nullptr; // {look-back spin ran out, largest group, key outside the optimistic range}
   bool lb_done = false;
+  // (route witnesses: the form of this attempt — the records are counted where the form is known, below)
+  ctx->order_route[lb ? Ctx::OR_LOOKBACK : Ctx::OR_COUNTING]++;
+  ctx->order_route[Ctx::OR_NARROW_HBM_ONLY] += hbm_only;
   if (lb) {
     ProfScope ps(ctx, "order_split");
     ghb = ctx->alloc(4 * 520);
@@ -435,6 +454,8 @@ static bool order_fast_impl(Ctx *ctx, const DCol &key, int desc, const DCol *car
     // (a carried column: word and value take turns in one LDS tile, the TWO form of ow_scatter_kernel)
     const char *slim_e = hook("SQLRS_ORDER_SLIM"); // (A/B hook, read per call: 0 = 16-byte records {word, value} between the passes)
     slim = NPAY == 1 && !want_perm && !(slim_e && slim_e[0] == '0'); // 12-byte records {key offset, value}: nobody reads the row id
+    ctx->order_route[Ctx::OR_REC12] += slim;
+    ctx->order_route[Ctx::OR_REC16] += NPAY == 1 && !slim;
     if (slim)
       ow_scatter_kernel<KIND, true, NPAY, false, NPAY == 1, false, true, NPAY == 1, NPAY == 1><<<g, b, 0, ctx->stream>>>(
           src, psrc, n, desc, imin, s1, nblocks, nullptr, out1, nullptr, nullptr, oob_lb, gh, lbdesc->as<uint32_t>(), nullptr, lbw);
@@ -466,6 +487,7 @@ static bool order_fast_impl(Ctx *ctx, const DCol &key, int desc, const DCol *car
     lb_done = true;
   } else
     for (int shift = 32 + rbits; shift < 32 + kbits || raw; shift += 8) one_pass(shift); // (>= 1 pass: the words must exist)
+  if (!lb) ctx->order_route[Ctx::OR_REC16] += rec_in || rec_form;
   const uint64_t *words = (const uint64_t *)src;
   const uint64_t *pays = psrc;
   // outputs
@@ -492,6 +514,7 @@ static bool order_fast_impl(Ctx *ctx, const DCol &key, int desc, const DCol *car
       carry_out->own_values = (pays == pa->as<uint64_t>()) ? pa : pb;
       carry_out->values = carry_out->own_values->p;
     }
+    ctx->order_route[Ctx::OR_NARROW]++;
     return true;
   }
   // 2. groups = distinct values of the top bits
@@ -579,6 +602,7 @@ static bool order_fast_impl(Ctx *ctx, const DCol &key, int desc, const DCol *car
 #undef SQ_FIN
     SQ_HIP(hipGetLastError());
   }
+  ctx->order_route[Ctx::OR_NARROW]++;
   return true;
 }
 
@@ -595,6 +619,7 @@ bool order_fast(Ctx *ctx, const DCol &key, int desc, const DCol *carry, int64_t 
   // optimistic key range for large columns (SQLRS_ORDER_SAMPLE, read per call: 0 = always the exact pass, 1 = always sampled)
   const char *smp_e = hook("SQLRS_ORDER_SAMPLE");
   const bool optimistic = smp_e ? std::atoi(smp_e) != 0 : n >= (1ll << 24); // (1 = whatever the size: tests)
+  ctx->order_route[Ctx::OR_SAMPLED] += optimistic;
 #define SQ_OF(K)                                                                                                     \
   do {                                                                                                               \
     bool retry = false, hbm = false;                                                                                 \
@@ -602,6 +627,7 @@ bool order_fast(Ctx *ctx, const DCol &key, int desc, const DCol *carry, int64_t 
                     : order_fast_impl<K, 0>(ctx, key, desc, nullptr, n, key_out, carry_out, perm, want_perm, optimistic, &retry, in_order, false, &hbm); \
     if (ok || (!retry && !hbm)) return ok;                                                                           \
     if (retry) {                                                                                                     \
+      ctx->order_route[Ctx::OR_SAMPLE_MISSED]++;                                                                     \
       retry = false;                                                                                                 \
       ok = carry ? order_fast_impl<K, 1>(ctx, key, desc, carry, n, key_out, carry_out, perm, want_perm, false, &retry, nullptr, false, &hbm) \
                  : order_fast_impl<K, 0>(ctx, key, desc, nullptr, n, key_out, carry_out, perm, want_perm, false, &retry, nullptr, false, &hbm); \
@@ -724,7 +750,10 @@ bool order_composite(Ctx *ctx, const std::vector<const DCol *> &keys, const std:
     ck.bits[c] = hi == lo ? 0 : 64 - __builtin_clzll(hi - lo);
     total += ck.bits[c] + (ck.valid[c] ? 1 : 0);
   }
-  if (total > 64) return false; // the composite does not fit one word: general path
+  if (total > 64) { // the composite does not fit one word: general path
+    ctx->order_route[Ctx::OR_COMPOSITE_TOO_WIDE]++;
+    return false;
+  }
   std::vector<int64_t> nulls((size_t)nk, 0);
   for (int c = 0; c < nk; c++)
     if (ck.valid[c]) nulls[(size_t)c] = count_nulls(ctx, *keys[(size_t)c]);
@@ -766,6 +795,8 @@ bool order_composite(Ctx *ctx, const std::vector<const DCol *> &keys, const std:
     }
     SQ_HIP(hipGetLastError());
   }
+  ctx->order_route[Ctx::OR_COMPOSITE]++;
+  ctx->order_route[Ctx::OR_COMPOSITE_NULLABLE] += any_nullable;
   return true;
 }
 

@@ -1,11 +1,14 @@
 """ORDER BY one key column on the fast route of order_fast.hip (rows travel through <= 2 HBM passes on the
-top key bits + an in-LDS finish) against the oracle (order.rs:15-67), including the shapes that must fall
-back to the general path.  A row-id column makes tie order (stable, like the general path) visible."""
+top key bits + an in-LDS finish) against the oracle (order.rs:15-67), including the shapes that take the splitter
+route or return their input as it came.  A row-id column makes tie order (stable, like the general path) visible.
+test_order_fast_route asserts the route by witness (order_plan.py restates the dispatch; tests/test_gpu_order_edges.py
+does so for every route and edge value)."""
 import os
 import numpy as np
 import pyarrow as pa
 import pytest
 
+import order_plan
 from sqlrs_amd import abi
 from sqlrs_amd.executor import LimitExecutor, OrderExecutor
 from sqlrs_amd.expr import InputRef, OrderBy
@@ -23,15 +26,15 @@ def keys_of(rng, shape):
         return rng.integers(-500, 500, N, dtype=np.int64)
     if shape == "i64_offset_2p40":
         return (1 << 40) + rng.integers(0, 1 << 24, N, dtype=np.int64)
-    if shape == "i64_wide":                  # > 32 varying bits: general path
+    if shape == "i64_wide":                  # > 32 varying bits: the splitter route (order_wide)
         return rng.integers(-(1 << 62), 1 << 62, N, dtype=np.int64)
-    if shape == "i64_heavy_groups":          # 50 distinct keys spread over 2^26: a group exceeds the LDS finish -> general path
+    if shape == "i64_heavy_groups":          # 50 distinct keys spread over 2^26: the heavy-value probe sends them to the splitter route, every group is copied
         return rng.choice(rng.integers(0, 1 << 26, 50, dtype=np.int64), N)
-    if shape == "i64_constant":
+    if shape == "i64_constant":             # in the requested order already: returned as it came
         return np.full(N, 7, dtype=np.int64)
-    if shape == "f64_unit":                  # doubles in [0, 1): 52 varying bits -> general path
+    if shape == "f64_unit":                  # doubles in [0, 1): 52 varying bits -> the splitter route
         return rng.random(N)
-    if shape == "f64_few":                   # doubles from a small set over a narrow bit range
+    if shape == "f64_few":                   # 4096 doubles in [1, 2): they differ in mantissa bits 40..51 -> the splitter route
         return (rng.integers(0, 4096, N) / 4096.0 + 1.0)
     if shape == "i32":
         return rng.integers(-(1 << 20), 1 << 20, N).astype(np.int32)
@@ -57,10 +60,20 @@ def test_order_fast_route(hip, oracle, shape, asc, extra):
         names += ["f", "i", "s"]
     b = pa.RecordBatch.from_arrays(cols, names=names)
     bs = [b.slice(0, N // 3), b.slice(N // 3)]
+    before = order_plan.read_counters(hip)
     (got,) = list(OrderExecutor(hip, [OrderBy(InputRef(0), asc=asc)], bs).execute())
+    after = order_plan.read_counters(hip)
     (exp,) = list(OrderExecutor(oracle, [OrderBy(InputRef(0), asc=asc)], bs).execute())
     for i in range(b.num_columns):
         assert got.column(i).equals(exp.column(i)), names[i]
+    # the route, by witness: exactly one of general / narrow / wide / in-order, the one the restated dispatch plans
+    plan = order_plan.Plan({})
+    plan.finish(pa.Table.from_batches([b]), [OrderBy(InputRef(0), asc=asc)])
+    want = {"i64_wide": "wide", "i64_heavy_groups": "wide", "f64_unit": "wide", "f64_few": "wide", "i64_constant": "in_order"}.get(shape, "narrow")
+    for r in ("general", "narrow", "wide", "in_order", "heavy_to_wide", "narrow_hbm_only"):
+        moved = after.get("order_" + r, 0) - before.get("order_" + r, 0)
+        assert moved == plan.c[r], (r, moved, dict(plan.c))
+    assert plan.c[want] == 1, (want, dict(plan.c))
 
 
 def hash_seed(*parts):
