@@ -256,13 +256,15 @@ impl HipHashAggExecutor {
 
 // ------------------------------------------------------------------- Order --
 /// `limit_hint`: a LimitExecutor sits directly above (PhysicalLimit(PhysicalOrder(child))) and reads only the first
-/// offset + limit rows: the operator may return a prefix of the sorted result (sqlrs_order_set_limit); 0 = no hint
-pub struct HipOrderExecutor { pub ctx: Arc<HipCtx>, pub order_by: Vec<BoundOrderBy>, pub child: BoxedExecutor, pub limit_hint: i64 }
+/// offset + limit rows: the operator may return a prefix of the sorted result (sqlrs_order_set_limit); 0 = no hint.
+/// `limit_all_keys` (SQLRS_ORDER_LIMIT_ALL_KEYS in `reserved` of the first key, opt-in): the hint also serves a Utf8 / nullable / expression first key.
+pub struct HipOrderExecutor { pub ctx: Arc<HipCtx>, pub order_by: Vec<BoundOrderBy>, pub child: BoxedExecutor, pub limit_hint: i64, pub limit_all_keys: bool }
 impl HipOrderExecutor {
     #[try_stream(boxed, ok = RecordBatch, error = ExecutorError)]
     pub async fn execute(self) {
         let low: Vec<Lowered> = self.order_by.iter().map(|o| lower(&o.expr)).collect::<Result<_, _>>()?;
-        let ob: Vec<sqlrs_order_by_t> = self.order_by.iter().zip(&low).map(|(o, l)| sqlrs_order_by_t { expr: l.abi(), asc: o.asc as i32, reserved: 0 }).collect();
+        let mut ob: Vec<sqlrs_order_by_t> = self.order_by.iter().zip(&low).map(|(o, l)| sqlrs_order_by_t { expr: l.abi(), asc: o.asc as i32, reserved: 0 }).collect();
+        if self.limit_all_keys { if let Some(first) = ob.first_mut() { first.reserved = SQLRS_ORDER_LIMIT_ALL_KEYS; } }
         let mut h = std::ptr::null_mut();
         self.ctx.check(unsafe { sqlrs_order_create(self.ctx.raw(), ob.len() as i32, ob.as_ptr(), &mut h) })?;
         let _g = Guard(h, sqlrs_order_destroy);
@@ -603,7 +605,7 @@ impl ExecutorBuilder {
         Some(HipHashAggExecutor { ctx: self.hip.clone(), agg_funcs: plan.logical().agg_funcs(), group_by: plan.logical().group_by(), child, child_filter }.execute())
     }
     pub fn hip_visit_physical_order(&mut self, plan: &PhysicalOrder) -> Option<BoxedExecutor> {
-        Some(HipOrderExecutor { ctx: self.hip.clone(), order_by: plan.logical().order_by(), child: self.visit(plan.children().first().unwrap().clone()).unwrap(), limit_hint: 0 }.execute())
+        Some(HipOrderExecutor { ctx: self.hip.clone(), order_by: plan.logical().order_by(), child: self.visit(plan.children().first().unwrap().clone()).unwrap(), limit_hint: 0, limit_all_keys: false }.execute())
     }
     pub fn hip_visit_physical_project(&mut self, plan: &PhysicalProject) -> Option<BoxedExecutor> {
         Some(HipProjectExecutor { ctx: self.hip.clone(), exprs: plan.logical().exprs(), child: self.visit(plan.children().first().unwrap().clone()).unwrap() }.execute())
@@ -613,6 +615,10 @@ impl ExecutorBuilder {
                                     join_output_schema: plan.join_output_columns() }.execute())
     }
     pub fn hip_visit_physical_limit(&mut self, plan: &PhysicalLimit) -> Option<BoxedExecutor> {
+        self.hip_visit_physical_limit_with(plan, false)
+    }
+    /// `order_limit_all_keys`: the opt-in SQLRS_ORDER_LIMIT_ALL_KEYS for the Order the peephole builds
+    pub fn hip_visit_physical_limit_with(&mut self, plan: &PhysicalLimit, order_limit_all_keys: bool) -> Option<BoxedExecutor> {
         // both bounds are Constants in the reference (limit.rs:14-27); the binder has already folded them
         let as_usize = |e: Option<BoundExpr>| e.and_then(|e| match e { BoundExpr::Constant(v) => v.as_usize(), e => unreachable!("expr: {:?} not allowed in limit", e) });
         let (limit, offset) = (as_usize(plan.logical().limit()), as_usize(plan.logical().offset()));
@@ -621,7 +627,7 @@ impl ExecutorBuilder {
         let child = match (below.as_physical_order(), limit) {
             (Ok(order), Some(l)) => HipOrderExecutor { ctx: self.hip.clone(), order_by: order.logical().order_by(),
                                                       child: self.visit(order.children().first().unwrap().clone()).unwrap(),
-                                                      limit_hint: (l + offset.unwrap_or(0)) as i64 }.execute(),
+                                                      limit_hint: (l + offset.unwrap_or(0)) as i64, limit_all_keys: order_limit_all_keys }.execute(),
             _ => self.visit(below).unwrap(),
         };
         Some(HipLimitExecutor { ctx: self.hip.clone(), limit, offset, child }.execute())

@@ -625,6 +625,7 @@ struct OrderExecutor { // order.rs:8-11
   // LimitExecutor directly above (PhysicalLimit(PhysicalOrder(child))): only the first offset + limit rows will be
   // read, the operator may return a prefix of the sorted result (sqlrs_order_set_limit); 0 = no hint
   int64_t limit_hint = 0;
+  bool limit_all_keys = false; // SQLRS_ORDER_LIMIT_ALL_KEYS on the first key: the hint also serves a Utf8 / nullable / expression first key
   BoxedExecutor execute() {
     struct S : Executor {
       HipCtxRef ctx; BoxedExecutor child; sqlrs_order_t *o = nullptr; bool done = false;
@@ -648,7 +649,7 @@ struct OrderExecutor { // order.rs:8-11
     std::vector<detail::Lowered> low;
     std::vector<sqlrs_order_by_t> ob;
     for (auto &x : order_by) low.push_back(detail::lower(x.expr));
-    for (size_t i = 0; i < order_by.size(); i++) ob.push_back(sqlrs_order_by_t{low[i].abi(), order_by[i].asc, 0});
+    for (size_t i = 0; i < order_by.size(); i++) ob.push_back(sqlrs_order_by_t{low[i].abi(), order_by[i].asc, (i == 0 && limit_all_keys) ? SQLRS_ORDER_LIMIT_ALL_KEYS : 0});
     ctx->check(sqlrs_order_create(ctx->raw, (int)ob.size(), ob.data(), &s->o));
     if (limit_hint > 0) ctx->check(sqlrs_order_set_limit(s->o, limit_hint));
     return s;
@@ -983,6 +984,7 @@ struct PlanNode {
 struct ExecutorBuilder {
   HipCtxRef ctx;
   bool fuse_join_agg = true; // false = one executor per node, as the reference builds them
+  bool order_limit_all_keys = false; // opt-in: the ORDER BY ... LIMIT peephole also serves Utf8 / nullable / expression first keys
   int64_t last_fused_batches = 0, last_filter_fused_batches = 0;
   int rewrites = 0;
 
@@ -1072,6 +1074,7 @@ struct ExecutorBuilder {
       OrderExecutor ord;
       ord.ctx = ctx; ord.order_by = child->order_by; ord.child = visit(child->children().front());
       ord.limit_hint = (int64_t)(*plan.limit + (plan.offset ? *plan.offset : 0));
+      ord.limit_all_keys = order_limit_all_keys;
       ex.child = ord.execute();
       rewrites++;
     } else {

@@ -176,7 +176,7 @@ typedef struct sqlrs_agg_func {
 typedef struct sqlrs_order_by {
   sqlrs_expr_t expr;
   int32_t asc;
-  int32_t reserved;
+  int32_t reserved; /* 0, or on the first key of sqlrs_order_create: SQLRS_ORDER_LIMIT_ALL_KEYS (see sqlrs_order_set_limit) */
 } sqlrs_order_by_t;
 
 /* ---------------------------------------------------------------- context -- */
@@ -536,6 +536,20 @@ int sqlrs_order_finish(sqlrs_order_t *o, int out_mem, sqlrs_batch_t **out);
  * small part of the input; ignored otherwise (0 = no hint).  The LimitExecutor above
  * slices either result the same way. */
 int sqlrs_order_set_limit(sqlrs_order_t *o, int64_t rows);
+/* Opt-in, SQLRS_ORDER_LIMIT_ALL_KEYS in `reserved` of the FIRST sqlrs_order_by_t handed to sqlrs_order_create (0, the
+ * default, leaves every decision of sqlrs_order_finish as it is): the hint of sqlrs_order_set_limit — under the same
+ * conditions on `rows` and the input size — also applies when the FIRST key is an Int32 / Int64 / Float64 column WITH NULLs,
+ * a Utf8 column (with or without NULLs), or an expression that is not a bare column reference and evaluates to one of those
+ * types (evaluated once over the whole input; an evaluation error is the one the full sort raises, same status and text).
+ * The contract is the same: the caller reads only the first `rows` rows; the result is a PREFIX of the full sorted result
+ * with at least `rows` rows, or everything; ties are stable and NULLs come first in either direction.  The threshold is a
+ * sampled row of the first key; a row is compared with it through a weak image — NULL below every valid row, a fixed-width
+ * key its value, a Utf8 key its first 64 bytes (zero padded) — and rows that tie with the threshold's image are kept, so no
+ * row that belongs to the prefix is lost.  The hint is ignored (everything is sorted) when fewer than `rows` rows qualify or
+ * more than half of the input does.  A Boolean first key, a constant first key and a first key sqlrs_order_set_limit serves
+ * by itself keep their routes.  (A flag of the create call, not an entry point of its own: the set of functions is
+ * unchanged.) */
+#define SQLRS_ORDER_LIMIT_ALL_KEYS 1
 /* rows the last finish sorted because of the hint; 0 = the hint did not apply (diagnostics / tests) */
 int64_t sqlrs_order_topk_candidates(const sqlrs_order_t *o);
 void sqlrs_order_destroy(sqlrs_order_t *o);

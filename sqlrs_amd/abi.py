@@ -19,6 +19,7 @@ import pyarrow as pa
 OK, ERR_ARROW, ERR_INTERNAL, ERR_STORAGE, ERR_DEVICE = 0, 1, 2, 3, 4
 NULLTYPE, INT32, INT64, FLOAT64, BOOLEAN, UTF8, UINT32, UINT64 = range(8)
 MEM_HOST, MEM_DEVICE = 0, 1
+ORDER_LIMIT_ALL_KEYS = 1  # SQLRS_ORDER_LIMIT_ALL_KEYS: `reserved` of the first OrderBy of order_create
 GROUP_ORDER_FIRST_SEEN, GROUP_ORDER_ANY = 0, 1
 JOIN_INNER, JOIN_LEFT, JOIN_RIGHT, JOIN_FULL = 0, 1, 2, 3
 AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX = 0, 1, 2, 3

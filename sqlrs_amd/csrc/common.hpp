@@ -222,6 +222,7 @@ struct Ctx {
     OR_NULL_SPLIT,     // order_null_split produced the result (the valid rows through an inner Order)
     OR_TOPK, OR_TOPK_IGNORED, // order_topk produced the candidates / ran and found fewer than the limit: hint ignored
     OR_ALLOC_DECLINED, // a fast attempt ran out of pool memory and was treated as "route not taken"
+    OR_TOPK_KEYS, OR_TOPK_KEYS_IGNORED, // order_topk_keys (SQLRS_ORDER_LIMIT_ALL_KEYS) produced the candidates / ran and a guard ignored the hint
     OR_COUNT_
   };
   int64_t order_route[OR_COUNT_] = {};

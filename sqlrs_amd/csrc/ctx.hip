@@ -1295,7 +1295,7 @@ int sqlrs_ctx_profile_read(sqlrs_ctx_t *ctx, int cap, const char **names, double
       "order_rec12", "order_rec16", "order_wide", "order_wide_declined", "order_wide_pure_copy", "order_wide_finish2",
       "order_wide_finish3", "order_heavy_to_wide", "order_range_sampled", "order_range_missed", "order_in_order",
       "order_composite", "order_composite_nullable", "order_composite_too_wide", "order_null_split", "order_topk",
-      "order_topk_ignored", "order_alloc_declined"};
+      "order_topk_ignored", "order_alloc_declined", "order_topk_keys", "order_topk_keys_ignored"};
   for (int r = 0; r < Ctx::OR_COUNT_; r++) {
     if (!ctx->order_route[r]) continue;
     if (n < cap) {

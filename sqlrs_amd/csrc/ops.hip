@@ -657,6 +657,7 @@ struct sqlrs_order {
   std::vector<DBatch> batches;
   int64_t limit_hint = 0;      // sqlrs_order_set_limit: only the first `limit_hint` rows of the result will be read
   int64_t topk_candidates = 0; // rows the last finish() sorted because of the hint (0 = everything)
+  bool limit_all_keys = false; // SQLRS_ORDER_LIMIT_ALL_KEYS on the first key: the hint also serves Utf8 / nullable / expression first keys
 };
 
 namespace sq {
@@ -686,6 +687,25 @@ int sqlrs_order_create(sqlrs_ctx_t *ctx, int num_keys, const sqlrs_order_by_t *o
 int sqlrs_order_push(sqlrs_order_t *o, const sqlrs_batch_t *in);
 int sqlrs_order_finish(sqlrs_order_t *o, int out_mem, sqlrs_batch_t **out);
 void sqlrs_order_destroy(sqlrs_order_t *o);
+}
+
+// an Order on o's keys and directions, without hint: the inner sort of the candidates
+static int order_clone_keys(const sqlrs_order *o, sqlrs_order_t **out) {
+  std::vector<std::vector<sqlrs_expr_node_t>> kn;
+  std::vector<sqlrs_order_by_t> ob;
+  for (size_t k = 0; k < o->exprs.size(); k++) {
+    kn.push_back(o->exprs[k].nodes);
+    for (size_t q2 = 0; q2 < kn.back().size(); q2++)
+      kn.back()[q2].s = o->exprs[k].strings[q2].empty() ? nullptr : o->exprs[k].strings[q2].c_str();
+  }
+  for (size_t k = 0; k < o->exprs.size(); k++) {
+    sqlrs_order_by_t e;
+    e.expr = sqlrs_expr_t{kn[k].data(), (int32_t)kn[k].size(), 0};
+    e.asc = o->asc[k];
+    e.reserved = 0;
+    ob.push_back(e);
+  }
+  return sqlrs_order_create((sqlrs_ctx_t *)o->ctx, (int)ob.size(), ob.data(), out);
 }
 
 // true = `out` holds the sorted candidates (a prefix of the full result with at least limit_hint rows)
@@ -745,21 +765,7 @@ static bool order_topk(sqlrs_order *o, DBatch &all, int kc, int out_mem, sqlrs_b
     if (st != SQLRS_OK) fail(st, ctx->last_error);
     if (kept && kept->num_rows >= L) {
       // 3. sort the candidates (same keys, same directions, no hint)
-      std::vector<std::vector<sqlrs_expr_node_t>> kn;
-      std::vector<sqlrs_order_by_t> ob;
-      for (size_t k = 0; k < o->exprs.size(); k++) {
-        kn.push_back(o->exprs[k].nodes);
-        for (size_t q2 = 0; q2 < kn.back().size(); q2++)
-          kn.back()[q2].s = o->exprs[k].strings[q2].empty() ? nullptr : o->exprs[k].strings[q2].c_str();
-      }
-      for (size_t k = 0; k < o->exprs.size(); k++) {
-        sqlrs_order_by_t e;
-        e.expr = sqlrs_expr_t{kn[k].data(), (int32_t)kn[k].size(), 0};
-        e.asc = o->asc[k];
-        e.reserved = 0;
-        ob.push_back(e);
-      }
-      st = sqlrs_order_create((sqlrs_ctx_t *)ctx, (int)ob.size(), ob.data(), &tmp);
+      st = order_clone_keys(o, &tmp);
       if (st == SQLRS_OK) st = sqlrs_order_push(tmp, kept);
       if (st == SQLRS_OK) st = sqlrs_order_finish(tmp, out_mem, out);
       if (st != SQLRS_OK) fail(st, ctx->last_error);
@@ -773,6 +779,38 @@ static bool order_topk(sqlrs_order *o, DBatch &all, int kc, int out_mem, sqlrs_b
   }
   cleanup();
   return done;
+}
+
+// The same for a first key order_topk leaves out (SQLRS_ORDER_LIMIT_ALL_KEYS): `key` = the first ORDER BY key over the
+// rows of `all` — a Utf8 column, a fixed-width column with NULLs, or a key expression's value.  order_topk.hip finds the
+// candidates (one mask pass against a sampled threshold row) and hands back their row ids; every column is gathered by
+// them and an inner Order sorts the gathered rows on all keys.
+static bool order_topk_keys(sqlrs_order *o, const DBatch &all, const DCol &key, int out_mem, sqlrs_batch_t **out) {
+  Ctx *ctx = o->ctx;
+  BufP idx;
+  int64_t count = 0;
+  if (!order_topk_keys_select(ctx, key, o->asc[0] ? 0 : 1, all.rows, o->limit_hint, &idx, &count)) {
+    ctx->order_route[Ctx::OR_TOPK_KEYS_IGNORED]++;
+    return false;
+  }
+  DBatch cand;
+  cand.rows = count;
+  for (const DCol &c : all.cols) cand.cols.push_back(gather_column(ctx, c, idx->p, false, nullptr, count));
+  sqlrs_order_t *tmp = nullptr;
+  try {
+    int st = order_clone_keys(o, &tmp);
+    if (st != SQLRS_OK) fail(st, ctx->last_error);
+    tmp->batches.push_back(std::move(cand));
+    st = sqlrs_order_finish(tmp, out_mem, out);
+    if (st != SQLRS_OK) fail(st, ctx->last_error);
+  } catch (...) {
+    if (tmp) sqlrs_order_destroy(tmp);
+    throw;
+  }
+  sqlrs_order_destroy(tmp);
+  o->topk_candidates = count;
+  ctx->order_route[Ctx::OR_TOPK_KEYS]++;
+  return true;
 }
 
 // the columns of `all` listed in `which`, gathered by the permutation `perm` of a fast Order route: plain 8-byte columns
@@ -867,6 +905,7 @@ int sqlrs_order_create(sqlrs_ctx_t *ctx, int num_keys, const sqlrs_order_by_t *o
       o->exprs.push_back(expr_from_abi(&order_by[i].expr));
       o->asc.push_back(order_by[i].asc);
     }
+    o->limit_all_keys = num_keys > 0 && (order_by[0].reserved & SQLRS_ORDER_LIMIT_ALL_KEYS) != 0;
     *out = o.release();
   });
 }
@@ -951,6 +990,26 @@ int sqlrs_order_finish(sqlrs_order_t *o, int out_mem, sqlrs_batch_t **out) {
           const bool plain = (kcol.dtype == SQLRS_INT64 || kcol.dtype == SQLRS_FLOAT64 || kcol.dtype == SQLRS_INT32) && kcol.stride != 0 &&
                              !(kcol.validity && kcol.null_count != 0);
           if (plain && order_topk(o, all, kc0, out_mem, out)) return;
+        }
+      }
+      // (SQLRS_ORDER_LIMIT_ALL_KEYS: the same gate; a first key the route above does not serve — a Utf8 column, a
+      //  fixed-width column with NULLs, a key expression evaluated once over all rows.  A Boolean or constant first key stays
+      //  on the routes below.)
+      if (o->limit_all_keys && o->limit_hint > 0 && tk != 0 && !o->exprs.empty() &&
+          (tk == 1 ? n >= (1 << 17) : (n >= (1 << 20) && o->limit_hint <= n / 16))) {
+        auto sortable = [](const DCol &c) {
+          return c.dtype == SQLRS_INT64 || c.dtype == SQLRS_FLOAT64 || c.dtype == SQLRS_INT32 || c.dtype == SQLRS_UTF8;
+        };
+        if (o->exprs[0].nodes.size() == 1 && o->exprs[0].nodes[0].op == SQLRS_EXPR_INPUT_REF) {
+          const int kc0 = o->exprs[0].nodes[0].index;
+          if (kc0 >= 0 && (size_t)kc0 < all.cols.size()) {
+            const DCol &kcol = all.cols[(size_t)kc0];
+            const bool served_above = kcol.dtype != SQLRS_UTF8 && !(kcol.validity && kcol.null_count != 0);
+            if (sortable(kcol) && kcol.stride != 0 && !served_above && order_topk_keys(o, all, kcol, out_mem, out)) return;
+          }
+        } else {
+          const DCol kcol = eval_expr(ctx, o->exprs[0], colfn, n, true);
+          if (sortable(kcol) && kcol.stride != 0 && order_topk_keys(o, all, kcol, out_mem, out)) return;
         }
       }
     }

@@ -35,6 +35,9 @@ DCol compact_column(Ctx *ctx, const DCol &c, const Selection &s);
 // u32 row ids of the kept rows
 BufP selection_indices_u32(Ctx *ctx, const Selection &s);
 BufP selection_indices_u64(Ctx *ctx, const Selection &s);
+// range_partition.hip: u32 ids of the set bits of `bits` over `rows` rows into out[tile_off[t] ...) — tile_off = the exclusive
+// scan of the kept rows per TILE_ROWS tile; one wave per tile, a tile without a kept row costs one load
+void selection_rows_u32(Ctx *ctx, const uint64_t *bits, const uint64_t *tile_off, int64_t rows, uint32_t *out);
 
 // Fused C2 fast path: predicate `col OP constant` + order-preserving compaction of that
 // column in one pass.  Returns the Selection (bits + tile offsets) so that further columns
@@ -53,6 +56,9 @@ DCol copy_column(Ctx *ctx, const DCol &c); // deep copy into buffers owned by th
 // ops.hip: stable sort of the rows in `perm` by a Utf8 column (NULL rows tie); keys = n-element scratch
 void sort_perm_by_utf8(Ctx *ctx, const DCol &c, const uint64_t *valid, int desc, uint32_t *perm, uint64_t *keys,
                        int64_t n);
+// order_topk.hip: the ORDER BY ... LIMIT candidates of a first key of any sortable type (Utf8, NULLs): u32 ids of the rows at
+// or below a sampled threshold, in input order; false = a guard ignored the hint (fewer than `limit`, or more than n / 2)
+bool order_topk_keys_select(Ctx *ctx, const DCol &key, int desc, int64_t n, int64_t limit, BufP *idx, int64_t *count);
 DCol materialize_scalar(Ctx *ctx, const DCol &c, int64_t rows);
 // number of clear validity bits among the first `rows` rows
 int64_t count_clear_bits(Ctx *ctx, const uint64_t *bits, int64_t rows);

@@ -213,6 +213,14 @@ __global__ __launch_bounds__(BLOCK) void range_select_rows_kernel(const uint64_t
   }
 }
 
+void selection_rows_u32(Ctx *ctx, const uint64_t *bits, const uint64_t *tile_off, int64_t rows, uint32_t *out) {
+  ProfScope ps(ctx, "range_select_rows");
+  const int64_t nwords = ceil_div(std::max<int64_t>(rows, 1), 64), ntiles = ceil_div(rows, TILE_ROWS);
+  const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(ntiles, WAVES_PER_BLOCK), 1024);
+  range_select_rows_kernel<<<dim3(blocks), dim3(BLOCK), 0, ctx->stream>>>(bits, tile_off, nwords, ntiles, out);
+  SQ_HIP(hipGetLastError());
+}
+
 // range_select_mask_kernel's bits over tuples written to HBM (more than RS_MAXK keys); the bound in LDS
 __global__ __launch_bounds__(BLOCK) void range_below_kernel(const uint64_t *__restrict__ tup, int tw, int64_t n,
                                                             const uint64_t *__restrict__ bound, uint64_t *__restrict__ bits) {
@@ -603,14 +611,7 @@ extern "C" int sqlrs_range_select(sqlrs_ctx_t *ctx, const sqlrs_batch_t *in, int
     }
     // the kept rows' ids, then every column gathered by them (what compact_column does for Utf8)
     BufP idx = ctx->alloc(4 * (size_t)std::max<int64_t>(s.count, 1));
-    if (s.count) {
-      ProfScope ps(ctx, "range_select_rows");
-      const int64_t ntiles = ceil_div(n, TILE_ROWS);
-      const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(ntiles, WAVES_PER_BLOCK), 1024);
-      range_select_rows_kernel<<<dim3(blocks), dim3(BLOCK), 0, ctx->stream>>>(s.bits, s.tile_off->as<uint64_t>(), nwords,
-                                                                              ntiles, idx->as<uint32_t>());
-      SQ_HIP(hipGetLastError());
-    }
+    if (s.count) selection_rows_u32(ctx, s.bits, s.tile_off->as<uint64_t>(), n, idx->as<uint32_t>());
     DBatch o;
     o.rows = s.count;
     for (int c = 0; c < nc; c++) o.cols.push_back(gather_column(ctx, ib.col(c), idx->p, false, nullptr, s.count));

@@ -367,8 +367,12 @@ class OrderExecutor:
     does with its Arc'd arrays, order.rs:19-26; ``sqlrs_order_push_retained``)."""
 
     def __init__(self, backend: abi.Backend, order_by: List[OrderBy], child: Iterable,
-                 out_mem: int = abi.MEM_HOST, retain_inputs: bool = False, limit_hint: Optional[int] = None):
+                 out_mem: int = abi.MEM_HOST, retain_inputs: bool = False, limit_hint: Optional[int] = None,
+                 limit_all_keys: bool = False):
         self.backend, self.order_by, self.child, self.out_mem = backend, order_by, child, out_mem
+        # SQLRS_ORDER_LIMIT_ALL_KEYS on the first key: the hint also serves a Utf8 / nullable / expression first key (opt-in;
+        # only handed to a backend that takes the hint: the oracle runs unchanged)
+        self.limit_all_keys = limit_all_keys
         self.retain_inputs = retain_inputs
         # LimitExecutor{offset, limit} directly above (PhysicalLimit(PhysicalOrder(child))): only the first
         # offset + limit rows will be read — the operator may return a prefix of the sorted result (sqlrs_order_set_limit)
@@ -383,11 +387,13 @@ class OrderExecutor:
             p = ob.expr.pack()
             keep.append(p)
             obs.append(abi.OrderBy(p.abi, int(ob.asc), 0))
+        hinted = self.limit_hint is not None and hasattr(be.lib, be.prefix + "order_set_limit")  # (HIP library only)
+        if hinted and self.limit_all_keys and obs:
+            obs[0].reserved = abi.ORDER_LIMIT_ALL_KEYS
         arr = (abi.OrderBy * max(len(obs), 1))(*obs)
         h = C.c_void_p()
         be.check(be.fn("order_create")(be.ctx, len(obs), arr, C.byref(h)))
         names = None
-        hinted = self.limit_hint is not None and hasattr(be.lib, be.prefix + "order_set_limit")  # (HIP library only)
         try:
             if hinted:
                 be.check(be.fn("order_set_limit")(h, int(self.limit_hint)))
