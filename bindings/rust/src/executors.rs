@@ -160,6 +160,9 @@ pub struct HipHashJoinExecutor {
     pub join_type: JoinType,
     pub join_condition: JoinCondition,
     pub join_output_schema: Vec<ColumnCatalog>,
+    /// SQLRS_EXPR_STAGE_ALL_TYPES in `reserved` of the first key expression (opt-in): small HOST batches with Utf8 / Boolean
+    /// columns and NULLs are staged and uploaded together too
+    pub stage_all_types: bool,
 }
 fn join_keys(cond: &JoinCondition) -> Result<(Vec<BoundExpr>, Vec<BoundExpr>, Option<BoundExpr>), ExecutorError> {
     match cond { // hash_join.rs:129-134
@@ -176,7 +179,8 @@ impl HipHashJoinExecutor {
     #[try_stream(boxed, ok = RecordBatch, error = ExecutorError)]
     pub async fn execute(self) {
         let (lk, rk, filter) = join_keys(&self.join_condition)?;
-        let (_l1, lke) = lower_all(&lk)?;
+        let (_l1, mut lke) = lower_all(&lk)?;
+        if self.stage_all_types { if let Some(first) = lke.first_mut() { first.reserved = SQLRS_EXPR_STAGE_ALL_TYPES; } }
         let (_l2, rke) = lower_all(&rk)?;
         let flt = filter.as_ref().map(lower).transpose()?;
         let fe = flt.as_ref().map(|f| f.abi());
@@ -223,6 +227,9 @@ pub struct HipHashAggExecutor {
     /// FilterExecutor{expr, child} directly below the operator (filter.rs:7-25): handed to the library, which evaluates
     /// `column OP constant` inside its first partition pass and runs the Filter operator itself otherwise
     pub child_filter: Option<BoundExpr>,
+    /// SQLRS_EXPR_STAGE_ALL_TYPES in `reserved` of the first key expression (opt-in): small HOST batches with Utf8 / Boolean
+    /// columns and NULLs are staged and uploaded together too
+    pub stage_all_types: bool,
 }
 fn agg_funcs_of(exprs: &[BoundExpr]) -> Vec<BoundAggFunc> {
     exprs.iter().filter_map(|e| if let BoundExpr::AggFunc(a) = e { Some(a.clone()) } else { None }).collect() // hash_agg.rs:58-63
@@ -231,7 +238,8 @@ impl HipHashAggExecutor {
     #[try_stream(boxed, ok = RecordBatch, error = ExecutorError)]
     pub async fn execute(self) {
         let aggs = agg_funcs_of(&self.agg_funcs);
-        let (_l1, ge) = lower_all(&self.group_by)?;
+        let (_l1, mut ge) = lower_all(&self.group_by)?;
+        if self.stage_all_types { if let Some(first) = ge.first_mut() { first.reserved = SQLRS_EXPR_STAGE_ALL_TYPES; } }
         let (_l2, af) = lower_aggs(&aggs)?;
         let mut a = std::ptr::null_mut();
         self.ctx.check(unsafe { sqlrs_hash_agg_create(self.ctx.raw(), ge.len() as i32, ge.as_ptr(), af.len() as i32, af.as_ptr(), &mut a) })?;
@@ -258,13 +266,16 @@ impl HipHashAggExecutor {
 /// `limit_hint`: a LimitExecutor sits directly above (PhysicalLimit(PhysicalOrder(child))) and reads only the first
 /// offset + limit rows: the operator may return a prefix of the sorted result (sqlrs_order_set_limit); 0 = no hint.
 /// `limit_all_keys` (SQLRS_ORDER_LIMIT_ALL_KEYS in `reserved` of the first key, opt-in): the hint also serves a Utf8 / nullable / expression first key.
-pub struct HipOrderExecutor { pub ctx: Arc<HipCtx>, pub order_by: Vec<BoundOrderBy>, pub child: BoxedExecutor, pub limit_hint: i64, pub limit_all_keys: bool }
+/// `stage_all_types` (SQLRS_EXPR_STAGE_ALL_TYPES in `reserved` of the first key's expression, opt-in): small HOST batches with Utf8 /
+/// Boolean columns and NULLs are staged and uploaded together too.
+pub struct HipOrderExecutor { pub ctx: Arc<HipCtx>, pub order_by: Vec<BoundOrderBy>, pub child: BoxedExecutor, pub limit_hint: i64, pub limit_all_keys: bool, pub stage_all_types: bool }
 impl HipOrderExecutor {
     #[try_stream(boxed, ok = RecordBatch, error = ExecutorError)]
     pub async fn execute(self) {
         let low: Vec<Lowered> = self.order_by.iter().map(|o| lower(&o.expr)).collect::<Result<_, _>>()?;
         let mut ob: Vec<sqlrs_order_by_t> = self.order_by.iter().zip(&low).map(|(o, l)| sqlrs_order_by_t { expr: l.abi(), asc: o.asc as i32, reserved: 0 }).collect();
         if self.limit_all_keys { if let Some(first) = ob.first_mut() { first.reserved = SQLRS_ORDER_LIMIT_ALL_KEYS; } }
+        if self.stage_all_types { if let Some(first) = ob.first_mut() { first.expr.reserved = SQLRS_EXPR_STAGE_ALL_TYPES; } }
         let mut h = std::ptr::null_mut();
         self.ctx.check(unsafe { sqlrs_order_create(self.ctx.raw(), ob.len() as i32, ob.as_ptr(), &mut h) })?;
         let _g = Guard(h, sqlrs_order_destroy);
@@ -509,12 +520,16 @@ pub struct HipHashJoinAggExecutor {
     pub agg_funcs: Vec<BoundExpr>,
     pub group_by: Vec<BoundExpr>,
     pub probe_filter: Option<BoundExpr>,
+    /// SQLRS_EXPR_STAGE_ALL_TYPES in `reserved` of the first key expression (opt-in): small HOST batches with Utf8 / Boolean
+    /// columns and NULLs are staged and uploaded together too
+    pub stage_all_types: bool,
 }
 impl HipHashJoinAggExecutor {
     #[try_stream(boxed, ok = RecordBatch, error = ExecutorError)]
     pub async fn execute(self) {
         let (lk, rk, _) = join_keys(&self.join_condition)?;
-        let (_l1, lke) = lower_all(&lk)?;
+        let (_l1, mut lke) = lower_all(&lk)?;
+        if self.stage_all_types { if let Some(first) = lke.first_mut() { first.reserved = SQLRS_EXPR_STAGE_ALL_TYPES; } }
         let (_l2, rke) = lower_all(&rk)?;
         let aggs = agg_funcs_of(&self.agg_funcs);
         let (_l3, ge) = lower_all(&self.group_by)?;
@@ -573,6 +588,7 @@ impl ExecutorBuilder {
             join_type: plan.join_type(),
             join_condition: plan.join_condition(),
             join_output_schema: plan.join_output_columns(),
+            stage_all_types: false,
         }.execute())
     }
     /// HashAgg, with the two peepholes that reach the fused forms from a reference-shaped plan:
@@ -595,6 +611,7 @@ impl ExecutorBuilder {
                     agg_funcs: plan.logical().agg_funcs(),
                     group_by: plan.logical().group_by(),
                     probe_filter,
+                    stage_all_types: false,
                 }.execute());
             }
         }
@@ -602,10 +619,10 @@ impl ExecutorBuilder {
             Some(f) => (self.visit(f.children().first().unwrap().clone()).unwrap(), Some(f.logical().expr())),
             None => (self.visit(child).unwrap(), None),
         };
-        Some(HipHashAggExecutor { ctx: self.hip.clone(), agg_funcs: plan.logical().agg_funcs(), group_by: plan.logical().group_by(), child, child_filter }.execute())
+        Some(HipHashAggExecutor { ctx: self.hip.clone(), agg_funcs: plan.logical().agg_funcs(), group_by: plan.logical().group_by(), child, child_filter, stage_all_types: false }.execute())
     }
     pub fn hip_visit_physical_order(&mut self, plan: &PhysicalOrder) -> Option<BoxedExecutor> {
-        Some(HipOrderExecutor { ctx: self.hip.clone(), order_by: plan.logical().order_by(), child: self.visit(plan.children().first().unwrap().clone()).unwrap(), limit_hint: 0, limit_all_keys: false }.execute())
+        Some(HipOrderExecutor { ctx: self.hip.clone(), order_by: plan.logical().order_by(), child: self.visit(plan.children().first().unwrap().clone()).unwrap(), limit_hint: 0, limit_all_keys: false, stage_all_types: false }.execute())
     }
     pub fn hip_visit_physical_project(&mut self, plan: &PhysicalProject) -> Option<BoxedExecutor> {
         Some(HipProjectExecutor { ctx: self.hip.clone(), exprs: plan.logical().exprs(), child: self.visit(plan.children().first().unwrap().clone()).unwrap() }.execute())
@@ -627,7 +644,7 @@ impl ExecutorBuilder {
         let child = match (below.as_physical_order(), limit) {
             (Ok(order), Some(l)) => HipOrderExecutor { ctx: self.hip.clone(), order_by: order.logical().order_by(),
                                                       child: self.visit(order.children().first().unwrap().clone()).unwrap(),
-                                                      limit_hint: (l + offset.unwrap_or(0)) as i64, limit_all_keys: order_limit_all_keys }.execute(),
+                                                      limit_hint: (l + offset.unwrap_or(0)) as i64, limit_all_keys: order_limit_all_keys, stage_all_types: false }.execute(),
             _ => self.visit(below).unwrap(),
         };
         Some(HipLimitExecutor { ctx: self.hip.clone(), limit, offset, child }.execute())

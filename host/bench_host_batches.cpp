@@ -7,8 +7,10 @@
 //   ./bench_host_batches probe_general ...         outer joins / duplicate build keys through push_async (see bench_probe_general)
 //   ./bench_host_batches probe_keys ...            Utf8 keys, two-column keys, NULL probe keys through push_async (see bench_probe_keys)
 //   ./bench_host_batches filter_all_types ...      Utf8 / Boolean predicates through push_async (see bench_filter_all_types)
+//   ./bench_host_batches stage_types ...           the blocking operators over Utf8 / Boolean / NULL-bearing batches, SQLRS_EXPR_STAGE_ALL_TYPES off and on (see bench_stage_types)
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -1099,7 +1101,212 @@ static int bench_filter_all_types(int argc, char **argv) {
   return all_ok ? 0 : 1;
 }
 
+// ./bench_host_batches stage_types [rows = 2e6] [batch = 1024]
+// SQLRS_EXPR_STAGE_ALL_TYPES: the three blocking operators fed pageable host batches of {int64 k, float64 v, Utf8 s of 4-16 bytes
+// (about 1000 distinct), Boolean p}, 2 % NULLs in v and in s, each batch's offsets and bitmaps a window into one array.  Legs:
+//   hash_agg   GROUP BY s: sum(v), count(p)
+//   order      ORDER BY s, k
+//   join_build Inner join, build side = the batches, key s; then ONE probe batch of 4096 strings (one in 64 has partners)
+// Each leg runs with the flag off (the ordinary path: one upload per batch and buffer) and on, alternating in one process; after
+// a warm-up each, the median of 5; the wall clock ends when the operator's finish has put the result on the host.  The two
+// results of a leg must agree bit for bit (v is a multiple of 1/8: a SUM is exact in any order).  One JSON line per leg;
+// "faster" = on_ms < off_ms - off_spread_ms.
+static uint64_t digest_batch(const sqlrs_batch_t *o, uint64_t h) {
+  auto mix = [&](uint64_t x) { h = (h ^ x) * 0x100000001b3ull; };
+  if (!o) return h;
+  mix((uint64_t)o->num_rows);
+  for (int c = 0; c < o->num_columns; c++) {
+    const sqlrs_column_t &col = o->columns[c];
+    const uint8_t *valid = col.null_count ? (const uint8_t *)col.validity : nullptr;
+    mix((uint64_t)col.null_count);
+    for (int64_t r = 0; r < o->num_rows; r++) {
+      if (valid && !((valid[r >> 3] >> (r & 7)) & 1)) {
+        mix(0x6e756c6cull);
+        continue;
+      }
+      if (col.dtype == SQLRS_UTF8) {
+        const int32_t *off = (const int32_t *)col.offsets;
+        const uint8_t *b = (const uint8_t *)col.values;
+        mix((uint64_t)(off[r + 1] - off[r]));
+        for (int32_t k = off[r]; k < off[r + 1]; k++) mix(b[k]);
+      } else if (col.dtype == SQLRS_BOOLEAN)
+        mix((((const uint8_t *)col.values)[r >> 3] >> (r & 7)) & 1);
+      else
+        mix(((const uint64_t *)col.values)[r]); // (the 8-byte types of this mode)
+    }
+  }
+  return h;
+}
+
+static int bench_stage_types(int argc, char **argv) {
+  const int64_t n = argc > 2 ? (int64_t)std::atof(argv[2]) : 2000000, B = argc > 3 ? std::atoll(argv[3]) : 1024;
+  if (B % 8 != 0 || n < 1 || n * 16 > 2000000000ll) {
+    std::printf("{\"error\": \"stage_types: needs a batch size that is a multiple of 8 and at most 1.25e8 rows\"}\n");
+    return 2;
+  }
+  sqlrs_ctx_t *ctx = nullptr;
+  if (sqlrs_ctx_create(0, &ctx) != SQLRS_OK) {
+    std::printf("{\"error\": \"no device\"}\n");
+    return 2;
+  }
+  const int64_t IDS = 1000, nb = (n + B - 1) / B;
+  auto text_of = [](int64_t id, char *out) -> int32_t { // 4 hex digits of the id, then 0-12 letters
+    const int32_t len = 4 + (int32_t)(id % 13);
+    std::memset(out, 'a' + (int)(id % 26), (size_t)len);
+    char hex[8];
+    std::snprintf(hex, sizeof(hex), "%04llx", (unsigned long long)(id & 0xffff));
+    std::memcpy(out, hex, 4);
+    return len;
+  };
+  std::vector<int64_t> k((size_t)n);
+  std::vector<double> v((size_t)n);
+  std::vector<int32_t> soff((size_t)n + 1, 0);
+  std::vector<char> sbytes((size_t)n * 16 + 16);
+  std::vector<uint8_t> vvalid((size_t)(n + 7) / 8 + 8, 0), svalid((size_t)(n + 7) / 8 + 8, 0), p((size_t)(n + 7) / 8 + 8, 0);
+  for (int64_t i = 0; i < n; i++) {
+    k[(size_t)i] = i;
+    v[(size_t)i] = (double)(splitmix64(0xB2, (uint64_t)i) % 8000) / 8.0;
+    const uint8_t bit = (uint8_t)(1u << (i & 7));
+    if (splitmix64(0xB3, (uint64_t)i) % 50 != 0) vvalid[(size_t)(i >> 3)] |= bit;
+    if (splitmix64(0xB4, (uint64_t)i) & 1) p[(size_t)(i >> 3)] |= bit;
+    int32_t len = 0;
+    if (splitmix64(0xB5, (uint64_t)i) % 50 != 0) {
+      svalid[(size_t)(i >> 3)] |= bit;
+      len = text_of((int64_t)(splitmix64(0xB6, (uint64_t)i) % (uint64_t)IDS), sbytes.data() + soff[(size_t)i]);
+    }
+    soff[(size_t)i + 1] = soff[(size_t)i] + len;
+  }
+  // the batches, built once: 4 columns each
+  std::vector<sqlrs_column_t> cols((size_t)nb * 4);
+  std::vector<sqlrs_batch_t> batches((size_t)nb);
+  for (int64_t b = 0; b < nb; b++) {
+    const int64_t lo = b * B, m = std::min<int64_t>(B, n - lo);
+    sqlrs_column_t *c = &cols[(size_t)b * 4];
+    host_col(c[0], SQLRS_INT64, k.data() + lo, m);
+    host_col(c[1], SQLRS_FLOAT64, v.data() + lo, m);
+    c[1].validity = vvalid.data() + lo / 8;
+    c[1].null_count = -1;
+    host_col(c[2], SQLRS_UTF8, sbytes.data(), m);
+    c[2].offsets = soff.data() + lo; // a window: offsets[0] != 0
+    c[2].validity = svalid.data() + lo / 8;
+    c[2].null_count = -1;
+    host_col(c[3], SQLRS_BOOLEAN, p.data() + lo / 8, m);
+    std::memset(&batches[(size_t)b], 0, sizeof(sqlrs_batch_t));
+    batches[(size_t)b].num_rows = m;
+    batches[(size_t)b].num_columns = 4;
+    batches[(size_t)b].columns = c;
+  }
+  // the join's probe batch: 4096 strings over 64 x the ids of the build side
+  const int64_t NP = 4096;
+  std::vector<int32_t> poff((size_t)NP + 1, 0);
+  std::vector<char> pbytes((size_t)NP * 16 + 16);
+  for (int64_t i = 0; i < NP; i++)
+    poff[(size_t)i + 1] = poff[(size_t)i] + text_of((int64_t)(splitmix64(0xB7, (uint64_t)i) % (uint64_t)(64 * IDS)), pbytes.data() + poff[(size_t)i]);
+  sqlrs_column_t pcol;
+  host_col(pcol, SQLRS_UTF8, pbytes.data(), NP);
+  pcol.offsets = poff.data();
+  sqlrs_batch_t probe{};
+  probe.num_rows = NP;
+  probe.num_columns = 1;
+  probe.columns = &pcol;
+
+  sqlrs_expr_node_t ref[4] = {};
+  for (int i = 0; i < 4; i++) {
+    ref[i].op = SQLRS_EXPR_INPUT_REF;
+    ref[i].index = i;
+  }
+  int rc_all = 0;
+  const char *leg_names[3] = {"hash_agg", "order", "join_build"};
+  for (int leg = 0; leg < 3; leg++) {
+    std::vector<double> ms[2];
+    uint64_t dig[2] = {0, 0};
+    int64_t out_rows[2] = {0, 0};
+    auto run = [&](int on, bool timed) -> int { // 0 ok
+      const int32_t flag = on ? SQLRS_EXPR_STAGE_ALL_TYPES : 0;
+      std::vector<sqlrs_batch_t *> outs;
+      auto t0 = std::chrono::steady_clock::now();
+      if (leg == 0) {
+        sqlrs_expr_t gb{&ref[2], 1, flag};
+        sqlrs_agg_func_t aggs[2] = {};
+        aggs[0].func = SQLRS_AGG_SUM;
+        aggs[0].return_dtype = SQLRS_FLOAT64;
+        aggs[0].arg = sqlrs_expr_t{&ref[1], 1, 0};
+        aggs[1].func = SQLRS_AGG_COUNT;
+        aggs[1].return_dtype = SQLRS_INT64;
+        aggs[1].arg = sqlrs_expr_t{&ref[3], 1, 0};
+        sqlrs_hash_agg_t *a = nullptr;
+        CHECK(sqlrs_hash_agg_create(ctx, 1, &gb, 2, aggs, &a));
+        for (int64_t b = 0; b < nb; b++) CHECK(sqlrs_hash_agg_push(a, &batches[(size_t)b]));
+        sqlrs_batch_t *o = nullptr;
+        CHECK(sqlrs_hash_agg_finish(a, SQLRS_MEM_HOST, &o));
+        outs.push_back(o);
+        sqlrs_hash_agg_destroy(a);
+      } else if (leg == 1) {
+        sqlrs_order_by_t ob[2] = {{sqlrs_expr_t{&ref[2], 1, flag}, 1, 0}, {sqlrs_expr_t{&ref[0], 1, 0}, 1, 0}};
+        sqlrs_order_t *od = nullptr;
+        CHECK(sqlrs_order_create(ctx, 2, ob, &od));
+        for (int64_t b = 0; b < nb; b++) CHECK(sqlrs_order_push(od, &batches[(size_t)b]));
+        sqlrs_batch_t *o = nullptr;
+        CHECK(sqlrs_order_finish(od, SQLRS_MEM_HOST, &o));
+        outs.push_back(o);
+        sqlrs_order_destroy(od);
+      } else {
+        sqlrs_expr_t lk{&ref[2], 1, flag}, rk{&ref[0], 1, 0};
+        const int32_t right_dtypes[1] = {SQLRS_UTF8};
+        sqlrs_hash_join_t *j = nullptr;
+        CHECK(sqlrs_hash_join_create(ctx, SQLRS_JOIN_INNER, 1, &lk, &rk, nullptr, 1, right_dtypes, &j));
+        for (int64_t b = 0; b < nb; b++) CHECK(sqlrs_hash_join_build_push(j, &batches[(size_t)b]));
+        CHECK(sqlrs_hash_join_build_finish(j));
+        sqlrs_batch_t *o = nullptr, *tail = nullptr;
+        CHECK(sqlrs_hash_join_probe_push(j, &probe, SQLRS_MEM_HOST, &o));
+        CHECK(sqlrs_hash_join_finish(j, SQLRS_MEM_HOST, &tail));
+        outs.push_back(o);
+        outs.push_back(tail);
+        sqlrs_hash_join_destroy(j);
+      }
+      const double t = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      if (timed) ms[on].push_back(t);
+      uint64_t h = 0xcbf29ce484222325ull;
+      out_rows[on] = 0;
+      for (sqlrs_batch_t *o : outs) {
+        h = digest_batch(o, h);
+        if (o) out_rows[on] += o->num_rows;
+        sqlrs_batch_release(o);
+      }
+      if (timed && h != dig[on]) dig[on] = ~0ull; // (a run that differs from its own warm-up)
+      if (!timed) dig[on] = h;
+      return 0;
+    };
+    for (int on = 0; on < 2; on++)
+      if (run(on, false)) return 1;
+    for (int rep = 0; rep < 5; rep++) // off and on alternate
+      for (int on = 0; on < 2; on++)
+        if (run(on, true)) return 1;
+    double med[2], spread[2];
+    for (int on = 0; on < 2; on++) {
+      std::sort(ms[on].begin(), ms[on].end());
+      med[on] = ms[on][2];
+      spread[on] = ms[on][4] - ms[on][0];
+    }
+    const bool ok = dig[0] == dig[1] && dig[0] != ~0ull && out_rows[0] == out_rows[1] && out_rows[0] > 0;
+    std::printf("{\"mode\": \"stage_types\", \"leg\": \"%s\", \"rows\": %lld, \"batches\": %lld, \"batch_rows\": %lld, \"out_rows\": %lld, "
+                "\"off_ms\": %.1f, \"off_spread_ms\": %.1f, \"on_ms\": %.1f, \"on_spread_ms\": %.1f, \"Mrows_s_off\": %.1f, \"Mrows_s_on\": %.1f, "
+                "\"on_over_off\": %.2f, \"faster\": %s, \"check\": \"%s\", \"note\": \"native caller (C ABI): pageable %lld-row host batches "
+                "{int64, float64, utf8 of 4-16 bytes, boolean}, 2 %% NULLs in the float64 and the utf8 column, result on the host; "
+                "SQLRS_EXPR_STAGE_ALL_TYPES off / on (alternating), median of 5 after a warm-up each, spread = max - min; on_over_off = "
+                "off_ms / on_ms; faster = on_ms < off_ms - off_spread_ms\"}\n",
+                leg_names[leg], (long long)n, (long long)nb, (long long)B, (long long)out_rows[1], med[0], spread[0], med[1], spread[1],
+                (double)n / med[0] / 1e3, (double)n / med[1] / 1e3, med[0] / med[1], med[1] < med[0] - spread[0] ? "true" : "false",
+                ok ? "OK" : "mismatch", (long long)B);
+    std::fflush(stdout);
+    if (!ok) rc_all = 1;
+  }
+  sqlrs_ctx_destroy(ctx);
+  return rc_all;
+}
+
 int main(int argc, char **argv) {
+  if (argc > 1 && std::strcmp(argv[1], "stage_types") == 0) return bench_stage_types(argc, argv);
   if (argc > 1 && std::strcmp(argv[1], "filter_all_types") == 0) return bench_filter_all_types(argc, argv);
   if (argc > 1 && std::strcmp(argv[1], "probe_filter") == 0) return bench_probe_filter(argc, argv);
   if (argc > 1 && std::strcmp(argv[1], "probe_keys") == 0) return bench_probe_keys(argc, argv);

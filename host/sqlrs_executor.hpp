@@ -471,6 +471,7 @@ struct HashJoinExecutor { // hash_join.rs:16-23
   bool async_utf8 = false;    // sqlrs_hash_join_set_async_utf8: with depth > 0, batches with Utf8 payload columns on either side in one launch too
   bool async_filter = false;  // sqlrs_hash_join_set_async_filter: with depth > 0, a join with a join filter in one launch per batch too (the filter inside the kernel)
   bool async_keys = false;    // sqlrs_hash_join_set_async_keys: with depth > 0, NULL probe keys, Utf8 keys (with async_utf8) and 2 to 4 key columns in one launch per batch too
+  bool stage_all_types = false; // SQLRS_EXPR_STAGE_ALL_TYPES on the first build key: small HOST build batches with Utf8 / Boolean columns and NULLs are staged too
 
   BoxedExecutor execute() {
     struct S : Executor {
@@ -551,6 +552,7 @@ struct HashJoinExecutor { // hash_join.rs:16-23
     for (auto &p : join_condition.on) { lk.push_back(detail::lower(p.first)); rk.push_back(detail::lower(p.second)); }
     for (auto &l : lk) lke.push_back(l.abi());
     for (auto &r : rk) rke.push_back(r.abi());
+    if (stage_all_types && !lke.empty()) lke[0].reserved = SQLRS_EXPR_STAGE_ALL_TYPES;
     detail::Lowered flt;
     sqlrs_expr_t fe{nullptr, 0, 0};
     if (join_condition.filter) { flt = detail::lower(*join_condition.filter); fe = flt.abi(); }
@@ -577,6 +579,7 @@ struct HashAggExecutor { // hash_agg.rs:15-19
   // (sqlrs_hash_agg_set_filter): same result as wrapping `child` in a FilterExecutor
   std::optional<BoundExpr> child_filter;
   int64_t *filter_fused_batches = nullptr; // out (optional): batches whose filter ran inside the first partition pass
+  bool stage_all_types = false; // SQLRS_EXPR_STAGE_ALL_TYPES on the first GROUP BY key: small HOST batches with Utf8 / Boolean columns and NULLs are staged too
 
   BoxedExecutor execute() {
     struct S : Executor {
@@ -604,6 +607,7 @@ struct HashAggExecutor { // hash_agg.rs:15-19
     std::vector<sqlrs_agg_func_t> af;
     for (auto &g : group_by) gl.push_back(detail::lower(g));
     for (auto &g : gl) ge.push_back(g.abi());
+    if (stage_all_types && !ge.empty()) ge[0].reserved = SQLRS_EXPR_STAGE_ALL_TYPES;
     for (auto &f : agg_funcs) al.push_back(detail::lower(f.exprs.at(0))); // only exprs[0] is read (hash_agg.rs:65)
     for (size_t i = 0; i < agg_funcs.size(); i++)
       af.push_back(sqlrs_agg_func_t{(int32_t)agg_funcs[i].func, agg_funcs[i].distinct, (int32_t)agg_funcs[i].return_type, 0, al[i].abi()});
@@ -626,6 +630,7 @@ struct OrderExecutor { // order.rs:8-11
   // read, the operator may return a prefix of the sorted result (sqlrs_order_set_limit); 0 = no hint
   int64_t limit_hint = 0;
   bool limit_all_keys = false; // SQLRS_ORDER_LIMIT_ALL_KEYS on the first key: the hint also serves a Utf8 / nullable / expression first key
+  bool stage_all_types = false; // SQLRS_EXPR_STAGE_ALL_TYPES on the first key's expression: small HOST batches with Utf8 / Boolean columns and NULLs are staged too
   BoxedExecutor execute() {
     struct S : Executor {
       HipCtxRef ctx; BoxedExecutor child; sqlrs_order_t *o = nullptr; bool done = false;
@@ -650,6 +655,7 @@ struct OrderExecutor { // order.rs:8-11
     std::vector<sqlrs_order_by_t> ob;
     for (auto &x : order_by) low.push_back(detail::lower(x.expr));
     for (size_t i = 0; i < order_by.size(); i++) ob.push_back(sqlrs_order_by_t{low[i].abi(), order_by[i].asc, (i == 0 && limit_all_keys) ? SQLRS_ORDER_LIMIT_ALL_KEYS : 0});
+    if (stage_all_types && !ob.empty()) ob[0].expr.reserved = SQLRS_EXPR_STAGE_ALL_TYPES;
     ctx->check(sqlrs_order_create(ctx->raw, (int)ob.size(), ob.data(), &s->o));
     if (limit_hint > 0) ctx->check(sqlrs_order_set_limit(s->o, limit_hint));
     return s;
@@ -866,6 +872,7 @@ struct HashJoinAggExecutor {
   std::vector<std::string> output_names;
   int64_t *fused_batches = nullptr, *filter_fused_batches = nullptr; // diagnostics, filled after the stream ends
   int64_t *eager_groups = nullptr; // partial groups re-aggregated by build-side GROUP BY columns (0 = route not taken)
+  bool stage_all_types = false; // SQLRS_EXPR_STAGE_ALL_TYPES on the first build key: both sides' small HOST batches with Utf8 / Boolean columns and NULLs are staged too
 
   BoxedExecutor execute() {
     struct S : Executor {
@@ -900,6 +907,7 @@ struct HashJoinAggExecutor {
     for (auto &p : join_condition.on) { lk.push_back(detail::lower(p.first)); rk.push_back(detail::lower(p.second)); }
     for (auto &l : lk) lke.push_back(l.abi());
     for (auto &r : rk) rke.push_back(r.abi());
+    if (stage_all_types) lke[0].reserved = SQLRS_EXPR_STAGE_ALL_TYPES;
     for (auto &g : group_by) gl.push_back(detail::lower(g));
     for (auto &g : gl) ge.push_back(g.abi());
     for (auto &f : agg_funcs) al.push_back(detail::lower(f.exprs.at(0)));

@@ -144,7 +144,7 @@ typedef struct sqlrs_expr_node {
 typedef struct sqlrs_expr {
   const sqlrs_expr_node_t *nodes; /* postfix order */
   int32_t num_nodes;
-  int32_t reserved;
+  int32_t reserved; /* 0, or on the first key expression of a blocking operator's create call: SQLRS_EXPR_STAGE_ALL_TYPES (see sqlrs_hash_agg_push) */
 } sqlrs_expr_t;
 
 /* [ref: src/binder/table/join.rs:18-24  enum JoinType] (Cross never reaches HashJoin:
@@ -488,7 +488,23 @@ int sqlrs_hash_agg_create(sqlrs_ctx_t *ctx, int num_group_by, const sqlrs_expr_t
  * by the call that works on the staged rows — a LATER push or *_finish — not necessarily by the push that delivered
  * the batch; the operator is unusable after an error either way (destroy it), exactly like the reference's stream,
  * which ends at its first Err.  A wide aggregate list (more than two argument columns) runs as several internal
- * operators that each see every batch. */
+ * operators that each see every batch.
+ *
+ * Opt-in, SQLRS_EXPR_STAGE_ALL_TYPES in `reserved` of the FIRST key expression handed to the create call — group_by[0] of
+ * sqlrs_hash_agg_create, left_keys[0] of sqlrs_hash_join_create, left_keys[0] of sqlrs_join_agg_create (its probe-side stage
+ * and the build side it owns), order_by[0].expr of sqlrs_order_create; 0, the default, leaves every decision as it is, and
+ * an aggregate without GROUP BY has no place for the flag: the staging area also takes small HOST batches with Utf8 and
+ * Boolean columns and with NULLs — what every table of the reference's own tests holds.  A batch is staged when it has at
+ * most 2^20 rows, every column is Int32 / Int64 / Float64 / Boolean / Utf8 (or an unsigned fixed-width type) of the staged
+ * schema's type, and every Utf8 column has offsets with 0 <= offsets[0] <= offsets[num_rows]; any other batch flushes the
+ * stage and is handled as without the flag, with the same status and message.  A push copies the batch's buffers as they are
+ * (no loop over rows); the flush — per 2^22 rows, before any Utf8 column would hold more than 2^30 staged bytes, or at
+ * *_finish — uploads every staged array once and builds each offsets array and bitmap with one kernel launch.  Results are
+ * those without the flag, bit for bit.  The caller's null_count is not trusted (it may be -1): the NULLs are counted on the
+ * staged validity bytes.  The error-reporting consequence above now applies to these batches too, which is why this is a
+ * flag.  sqlrs_ctx_profile_read reports the batches staged this way as "stage_all_types_batches" and the flushes that ran the
+ * kernels as "stage_stitch_flushes". */
+#define SQLRS_EXPR_STAGE_ALL_TYPES 1
 int sqlrs_hash_agg_push(sqlrs_hash_agg_t *a, const sqlrs_batch_t *in);
 /* [ref: hash_agg.rs:124-149]; with no pushed batch the reference panics (:125):
  * here that is SQLRS_ERR_INTERNAL. */

@@ -20,6 +20,8 @@ OK, ERR_ARROW, ERR_INTERNAL, ERR_STORAGE, ERR_DEVICE = 0, 1, 2, 3, 4
 NULLTYPE, INT32, INT64, FLOAT64, BOOLEAN, UTF8, UINT32, UINT64 = range(8)
 MEM_HOST, MEM_DEVICE = 0, 1
 ORDER_LIMIT_ALL_KEYS = 1  # SQLRS_ORDER_LIMIT_ALL_KEYS: `reserved` of the first OrderBy of order_create
+# SQLRS_EXPR_STAGE_ALL_TYPES: `reserved` of the first key Expr of hash_agg / hash_join / join_agg / order _create
+EXPR_STAGE_ALL_TYPES = 1
 GROUP_ORDER_FIRST_SEEN, GROUP_ORDER_ANY = 0, 1
 JOIN_INNER, JOIN_LEFT, JOIN_RIGHT, JOIN_FULL = 0, 1, 2, 3
 AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX = 0, 1, 2, 3
@@ -677,8 +679,11 @@ class Backend:
 
     def profile_read(self) -> dict:
         cap = 64
-        names = (C.c_char_p * cap)()
-        ms = (C.c_double * cap)()
-        n_l = (C.c_int64 * cap)()
-        n = self.fn("ctx_profile_read")(self.ctx, cap, names, ms, n_l)
-        return {names[k].decode(): (ms[k], n_l[k]) for k in range(min(n, cap))}
+        while True:  # the call returns how many entries there are: read again with room for all of them (a long-lived ctx with
+            names = (C.c_char_p * cap)()  # profiling scopes and every route count moved has more than 64, and the newest counts come last)
+            ms = (C.c_double * cap)()
+            n_l = (C.c_int64 * cap)()
+            n = self.fn("ctx_profile_read")(self.ctx, cap, names, ms, n_l)
+            if n <= cap:
+                return {names[k].decode(): (ms[k], n_l[k]) for k in range(n)}
+            cap = n + 16

@@ -278,6 +278,12 @@ static void copy_in(Ctx *ctx, void *dst, const void *src, size_t bytes, int mem)
                         ctx->stream));
 }
 
+// off[i] -= sub, i in [0, n]
+__global__ __launch_bounds__(256) void shift_offsets_kernel(int32_t *off, int64_t n, int32_t sub) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i <= n) off[i] -= sub;
+}
+
 DCol upload_column(Ctx *ctx, const sqlrs_column_t &c, bool force_copy) {
   DCol d;
   d.dtype = c.dtype;
@@ -315,7 +321,22 @@ DCol upload_column(Ctx *ctx, const sqlrs_column_t &c, bool force_copy) {
       ctx->sync();
     }
     d.data_bytes = last;
-    if (copy) {
+    // a HOST column whose offsets are a window into a longer array (offsets[0] = first != 0) is uploaded as the column it
+    // describes — the bytes [first, last), offsets from 0: concat_columns puts one part's bytes right behind the other's, and the
+    // bytes below `first` would land inside the last string of the part in front
+    const int32_t first = (c.mem == SQLRS_MEM_HOST && copy) ? c.offsets[0] : 0;
+    if (first > 0 && first <= last) {
+      d.data_bytes = last - first;
+      d.own_offsets = ctx->alloc(4 * (size_t)(c.length + 1));
+      copy_in(ctx, d.own_offsets->p, c.offsets, 4 * (size_t)(c.length + 1), c.mem);
+      shift_offsets_kernel<<<dim3((unsigned)ceil_div(c.length + 1, 256)), dim3(256), 0, ctx->stream>>>(d.own_offsets->as<int32_t>(),
+                                                                                                      c.length, first);
+      SQ_HIP(hipGetLastError());
+      d.offsets = d.own_offsets->as<int32_t>();
+      d.own_values = ctx->alloc((size_t)(last - first) + 8);
+      copy_in(ctx, d.own_values->p, (const uint8_t *)c.values + first, (size_t)(last - first), c.mem);
+      d.values = d.own_values->p;
+    } else if (copy) {
       d.own_offsets = ctx->alloc(4 * (size_t)(c.length + 1));
       copy_in(ctx, d.own_offsets->p, c.offsets, 4 * (size_t)(c.length + 1), c.mem);
       d.offsets = d.own_offsets->as<int32_t>();
@@ -549,8 +570,47 @@ sqlrs_batch_t *emit_host_copy(Ctx *ctx, int ncols, const int32_t *dtypes, int64_
 }
 
 // --------------------------------------------------------------- host staging --
+// SQLRS_EXPR_STAGE_ALL_TYPES: the two stitch launches of a flush (stage_stitch.hpp), one thread per output element
+__global__ __launch_bounds__(256) void stitch_bits_kernel(const uint8_t *__restrict__ raw, const int64_t *__restrict__ row_start,
+                                                          const int64_t *__restrict__ byte_start, int64_t P, int64_t rows,
+                                                          int64_t words, uint64_t *__restrict__ out) {
+  const int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (w < words) out[w] = stitch_bits_word(raw, row_start, byte_start, P, rows, w); // (words beyond the last row: 0, the padding)
+}
+__global__ __launch_bounds__(256) void stitch_offsets_kernel(const int32_t *__restrict__ raw_off, const int64_t *__restrict__ row_start,
+                                                             const int64_t *__restrict__ delta, int64_t P, int64_t rows,
+                                                             int64_t total_chars, int32_t *__restrict__ out) {
+  const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (r <= rows) out[r] = stitch_offset(raw_off, row_start, delta, P, rows, total_chars, r);
+}
+
+static int stitch_kind(int32_t dtype) { return dtype == SQLRS_UTF8 ? STITCH_UTF8 : dtype == SQLRS_BOOLEAN ? STITCH_BOOL : STITCH_FIXED; }
+static void *stitch_pin_alloc(size_t bytes) {
+  void *p = nullptr;
+  SQ_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+  return p;
+}
+static void stitch_pin_release(void *p) { (void)hipHostFree(p); }
+
 bool HostStage::accepts(const sqlrs_batch_t *b) const {
   if (!b || b->num_columns <= 0 || b->num_rows < 0 || b->num_rows > HOST_STAGE_MAX_BATCH) return false; // (< 0: InBatch rejects it)
+  if (all_types) {
+    if (has_schema && (size_t)b->num_columns != st.cols.size()) return false;
+    const int64_t n = b->num_rows;
+    for (int i = 0; i < b->num_columns; i++) {
+      const sqlrs_column_t &c = b->columns[i];
+      if (c.mem != SQLRS_MEM_HOST || c.length != n) return false;
+      if (!width_of(c.dtype) && c.dtype != SQLRS_BOOLEAN && c.dtype != SQLRS_UTF8) return false; // (NULLTYPE: the ordinary path)
+      if (has_schema && st_dtypes[(size_t)i] != c.dtype) return false;
+      if (c.dtype == SQLRS_UTF8) {
+        if (!c.offsets || c.offsets[0] < 0 || c.offsets[0] > c.offsets[n]) return false;
+        if (StitchStage::piece_over_cap(n, c.offsets, HOST_STAGE_FLUSH_CHARS)) return false;
+        if (!c.values && c.offsets[n] > c.offsets[0]) return false;
+      } else if (!c.values && n > 0)
+        return false;
+    }
+    return true;
+  }
   if (has_schema && (size_t)b->num_columns != cols.size()) return false;
   for (int i = 0; i < b->num_columns; i++) {
     const sqlrs_column_t &c = b->columns[i];
@@ -560,7 +620,43 @@ bool HostStage::accepts(const sqlrs_batch_t *b) const {
   return true;
 }
 
+// (only asked about a batch `accepts` took)
+bool HostStage::flush_before(const sqlrs_batch_t *b) {
+  if (!all_types || !has_schema) return false;
+  st_piece.resize((size_t)b->num_columns);
+  for (int i = 0; i < b->num_columns; i++) st_piece[(size_t)i].offsets = b->columns[i].offsets;
+  return st.would_pass_cap(b->num_rows, st_piece.data(), HOST_STAGE_FLUSH_CHARS);
+}
+
 void HostStage::append(const sqlrs_batch_t *b) {
+  if (all_types) {
+    if (!has_schema) {
+      std::vector<int> kinds((size_t)b->num_columns);
+      std::vector<size_t> widths((size_t)b->num_columns);
+      st_dtypes.resize((size_t)b->num_columns);
+      for (int i = 0; i < b->num_columns; i++) {
+        st_dtypes[(size_t)i] = b->columns[i].dtype;
+        kinds[(size_t)i] = stitch_kind(b->columns[i].dtype);
+        widths[(size_t)i] = width_of(b->columns[i].dtype);
+      }
+      st.mem = StitchMem{stitch_pin_alloc, stitch_pin_release};
+      st.pin_rows = HOST_STAGE_PIN_ROWS;
+      st.begin(b->num_columns, kinds.data(), widths.data());
+      has_schema = true;
+    }
+    std::vector<StitchPiece> &p = st_piece; // (a member: no allocation per push)
+    p.resize((size_t)b->num_columns);
+    for (int i = 0; i < b->num_columns; i++) {
+      const sqlrs_column_t &c = b->columns[i];
+      p[(size_t)i].values = c.values;
+      p[(size_t)i].validity = (c.validity && c.null_count != 0) ? c.validity : nullptr;
+      p[(size_t)i].offsets = c.offsets;
+    }
+    st.append(b->num_rows, p.data());
+    rows = st.rows;
+    ctx->stage_all_types_batches++;
+    return;
+  }
   if (!has_schema) {
     if (cols.size() != (size_t)b->num_columns) { // (column slots keep their pinned block across flushes of one schema)
       for (Col &c : cols)
@@ -632,8 +728,113 @@ void HostStage::append(const sqlrs_batch_t *b) {
   rows += n;
 }
 
+// SQLRS_EXPR_STAGE_ALL_TYPES: every raw array is uploaded once, one launch per bitmap / offset array stitches the pieces
+// (stage_stitch.hpp), and the columns are handed out as they stand in HBM.  Waits for the uploads before the staging arrays
+// are reused.
+sqlrs_batch_t *HostStage::take_all_types() {
+  const int64_t n = st.rows, P = st.pieces();
+  DBatch b;
+  b.rows = n;
+  // the piece tables of every launch, in one array and one upload: row_start, then per stitched array its byte_start / delta
+  std::vector<int64_t> tab(st.row_start);
+  std::vector<int64_t> nulls(st.cols.size(), 0);
+  std::vector<size_t> t_valid(st.cols.size(), 0), t_own(st.cols.size(), 0);
+  for (size_t i = 0; i < st.cols.size() && n > 0; i++) {
+    const StitchCol &c = st.cols[i];
+    if (c.valid.any) nulls[i] = stitch_count_clear(c.valid.raw.data(), st.row_start.data(), c.valid.byte_start.data(), P);
+    if (nulls[i]) {
+      t_valid[i] = tab.size();
+      tab.insert(tab.end(), c.valid.byte_start.begin(), c.valid.byte_start.end());
+    }
+    if (c.kind != STITCH_FIXED) {
+      t_own[i] = tab.size();
+      const std::vector<int64_t> &t = c.kind == STITCH_BOOL ? c.bits.byte_start : c.delta;
+      tab.insert(tab.end(), t.begin(), t.end());
+    }
+  }
+  sqlrs_batch_t *dev = nullptr;
+  try {
+    auto up = [&](void *dst, const void *src, size_t bytes) {
+      if (bytes) SQ_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    };
+    bool stitched = false;
+    ProfScope ps(ctx, "stage_stitch");
+    BufP dtab = ctx->alloc(8 * tab.size());
+    if (n > 0) up(dtab->p, tab.data(), 8 * tab.size());
+    const int64_t *d_row_start = dtab->as<int64_t>();
+    const int64_t words = ceil_div(n, 64) + 1; // (+ the padding word, written as 0)
+    auto stitch_bits = [&](const StitchBits &sb, size_t t) -> BufP {
+      BufP raw = ctx->alloc(sb.raw.size() + 16), out = ctx->alloc(bitmap_bytes(n) + 8);
+      up(raw->p, sb.raw.data(), sb.raw.size());
+      stitch_bits_kernel<<<dim3((unsigned)ceil_div(words, 256)), dim3(256), 0, ctx->stream>>>(
+          raw->as<uint8_t>(), d_row_start, dtab->as<int64_t>() + t, P, n, words, out->as<uint64_t>());
+      SQ_HIP(hipGetLastError());
+      stitched = true;
+      return out;
+    };
+    for (size_t i = 0; i < st.cols.size(); i++) {
+      const StitchCol &c = st.cols[i];
+      DCol d;
+      d.dtype = st_dtypes[i];
+      d.length = n;
+      if (n == 0) { // only 0-row batches were staged
+        d.own_values = ctx->alloc_zero(16);
+        d.values = d.own_values->p;
+        if (c.kind == STITCH_UTF8) {
+          d.own_offsets = ctx->alloc_zero(8);
+          d.offsets = d.own_offsets->as<int32_t>();
+        }
+        b.cols.push_back(std::move(d));
+        continue;
+      }
+      if (nulls[i]) {
+        d.own_validity = stitch_bits(c.valid, t_valid[i]);
+        d.validity = d.own_validity->as<uint64_t>();
+        d.null_count = nulls[i];
+      }
+      if (c.kind == STITCH_FIXED) {
+        d.own_values = ctx->alloc(c.width * (size_t)n + 16);
+        up(d.own_values->p, c.vals.data(), c.width * (size_t)n);
+      } else if (c.kind == STITCH_BOOL) {
+        d.own_values = stitch_bits(c.bits, t_own[i]);
+      } else {
+        const int64_t chars = c.chars();
+        d.data_bytes = chars;
+        d.own_values = ctx->alloc((size_t)chars + 8);
+        up(d.own_values->p, c.vals.data(), (size_t)chars);
+        BufP raw = ctx->alloc(c.offs.size() + 16); // 4 (n + P) bytes: every piece's n_k + 1 offsets
+        up(raw->p, c.offs.data(), c.offs.size());
+        d.own_offsets = ctx->alloc(4 * ((size_t)n + 1));
+        stitch_offsets_kernel<<<dim3((unsigned)ceil_div(n + 1, 256)), dim3(256), 0, ctx->stream>>>(
+            raw->as<int32_t>(), d_row_start, dtab->as<int64_t>() + t_own[i], P, n, chars, d.own_offsets->as<int32_t>());
+        SQ_HIP(hipGetLastError());
+        stitched = true;
+        d.offsets = d.own_offsets->as<int32_t>();
+      }
+      d.values = d.own_values->p;
+      b.cols.push_back(std::move(d));
+    }
+    if (stitched) ctx->stage_stitch_flushes++;
+    dev = emit_batch(ctx, std::move(b), SQLRS_MEM_DEVICE);
+  } catch (...) {
+    (void)hipStreamSynchronize(ctx->stream); // (uploads out of the staging arrays may be in flight)
+    throw;
+  }
+  try {
+    ctx->sync();
+  } catch (...) {
+    sqlrs_batch_release(dev);
+    throw;
+  }
+  st.clear();
+  has_schema = false;
+  rows = 0;
+  return dev;
+}
+
 sqlrs_batch_t *HostStage::take() {
   if (!has_schema) return nullptr;
+  if (all_types) return take_all_types();
   std::vector<sqlrs_column_t> descs(cols.size());
   for (size_t i = 0; i < cols.size(); i++) {
     sqlrs_column_t &d = descs[i];
@@ -772,6 +973,7 @@ void split_rows_to_host(Ctx *ctx, const DBatch &o, const std::vector<int64_t> &c
 HostStage::~HostStage() {
   for (Col &c : cols)
     if (c.pin) (void)hipHostFree(c.pin);
+  st.drop();
 }
 
 // Host columns built by the library itself (CSV ingest) -> library-owned HOST batch.  Every pointer of
@@ -1302,6 +1504,19 @@ int sqlrs_ctx_profile_read(sqlrs_ctx_t *ctx, int cap, const char **names, double
       names[n] = ORDER_ROUTE_NAMES[r];
       total_ms[n] = 0;
       launches[n] = ctx->order_route[r];
+    }
+    n++;
+  }
+  // (counts of SQLRS_EXPR_STAGE_ALL_TYPES, host_stage.hpp: the HOST batches a stage carrying the flag took, and the flushes that
+  //  ran the stitch kernels; behind every older entry)
+  const int64_t stage_counts[2] = {ctx->stage_all_types_batches, ctx->stage_stitch_flushes};
+  static const char *const STAGE_COUNT_NAMES[2] = {"stage_all_types_batches", "stage_stitch_flushes"};
+  for (int r = 0; r < 2; r++) {
+    if (!stage_counts[r]) continue;
+    if (n < cap) {
+      names[n] = STAGE_COUNT_NAMES[r];
+      total_ms[n] = 0;
+      launches[n] = stage_counts[r];
     }
     n++;
   }

@@ -749,7 +749,11 @@ static int hash_agg_create_impl(sqlrs_ctx_t *ctx, int num_group_by, const sqlrs_
                                 const sqlrs_agg_func_t *aggs, bool allow_split, sqlrs_hash_agg_t **out);
 int sqlrs_hash_agg_create(sqlrs_ctx_t *ctx, int num_group_by, const sqlrs_expr_t *group_by,
                           int num_aggs, const sqlrs_agg_func_t *aggs, sqlrs_hash_agg_t **out) {
-  return hash_agg_create_impl(ctx, num_group_by, group_by, num_aggs, aggs, true, out);
+  int st = hash_agg_create_impl(ctx, num_group_by, group_by, num_aggs, aggs, true, out);
+  // SQLRS_EXPR_STAGE_ALL_TYPES on group_by[0]: the operator the caller feeds stages every column type (host_stage.hpp); the
+  // operators the library creates for itself — parts, DISTINCT dedup, the eager pair — are fed device batches and stay as they are
+  if (st == SQLRS_OK) (*out)->hstage.all_types = stage_all_types_flag(num_group_by, group_by);
+  return st;
 }
 
 // Parts of a wide aggregate list (sqlrs_hash_agg::parts): the aggregates of ONE argument expression per part (first
@@ -886,7 +890,8 @@ int sqlrs_hash_agg_push(sqlrs_hash_agg_t *a, const sqlrs_batch_t *in) {
   if (!a->parts.empty()) a->saw_batch = true; // (wide aggregate list: staged here, handed to the parts by hash_agg_push_device)
   a->hstage.ctx = a->ctx;
   if (a->hstage.accepts(in)) {
-    int st = guard(a->ctx, [&] { a->hstage.append(in); });
+    int st = a->hstage.flush_before(in) ? hash_agg_flush_host(a) : SQLRS_OK; // (all types: the staged chars of a Utf8 column are capped)
+    if (st == SQLRS_OK) st = guard(a->ctx, [&] { a->hstage.append(in); });
     if (st != SQLRS_OK || a->hstage.rows < HOST_STAGE_FLUSH_ROWS) return st;
     return hash_agg_flush_host(a);
   }
@@ -1321,6 +1326,10 @@ int sqlrs_join_agg_create(sqlrs_ctx_t *ctx, int num_keys, const sqlrs_expr_t *le
     ja->join->lazy_table = true; // (join_state.hpp: built when the composed route first probes it)
     st = sqlrs_hash_agg_create(ctx, num_group_by, group_by, num_aggs, aggs, &ja->agg);
     if (st != SQLRS_OK) fail(st, ctx->last_error);
+    // SQLRS_EXPR_STAGE_ALL_TYPES on left_keys[0] (handed on to the join above: the build side this operator owns) also serves
+    // the probe-side stage; the aggregate inside is fed device batches whatever its group_by[0] carries
+    ja->hstage.all_types = stage_all_types_flag(num_keys, left_keys);
+    ja->agg->hstage.all_types = false;
     join_agg_plan_eager(ja.get(), num_keys, left_keys, right_keys, num_group_by, group_by, num_aggs, aggs);
     *out = ja.release();
   });
@@ -1511,7 +1520,9 @@ static int join_agg_flush_host(sqlrs_join_agg_t *ja) {
 int sqlrs_join_agg_probe_push(sqlrs_join_agg_t *ja, const sqlrs_batch_t *right) {
   ja->hstage.ctx = ja->ctx;
   if (ja->hstage.accepts(right)) {
-    int st = guard(ja->ctx, [&] {
+    int st = ja->hstage.flush_before(right) ? join_agg_flush_host(ja) : SQLRS_OK;
+    if (st != SQLRS_OK) return st;
+    st = guard(ja->ctx, [&] {
       if (!ja->join->finished) fail(SQLRS_ERR_INTERNAL, "probe before build_finish");
       ja->hstage.append(right);
     });

@@ -1115,6 +1115,7 @@ int sqlrs_hash_join_create(sqlrs_ctx_t *ctx, int join_type, int num_keys,
       j->filter = expr_from_abi(filter);
     }
     if (num_right_columns > 0) j->right_dtypes.assign(right_dtypes, right_dtypes + num_right_columns);
+    j->hstage.all_types = stage_all_types_flag(num_keys, left_keys); // SQLRS_EXPR_STAGE_ALL_TYPES: the build side's stage (host_stage.hpp)
     *out = j.release();
   });
 }
@@ -1135,7 +1136,8 @@ static int hash_join_flush_host(sqlrs_hash_join_t *j) {
 int sqlrs_hash_join_build_push(sqlrs_hash_join_t *j, const sqlrs_batch_t *left) {
   j->hstage.ctx = j->ctx;
   if (!j->finished && j->hstage.accepts(left)) {
-    int st = guard(j->ctx, [&] { j->hstage.append(left); });
+    int st = j->hstage.flush_before(left) ? hash_join_flush_host(j) : SQLRS_OK;
+    if (st == SQLRS_OK) st = guard(j->ctx, [&] { j->hstage.append(left); });
     if (st != SQLRS_OK || j->hstage.rows < HOST_STAGE_FLUSH_ROWS) return st;
     return hash_join_flush_host(j);
   }

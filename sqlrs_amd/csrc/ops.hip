@@ -906,6 +906,7 @@ int sqlrs_order_create(sqlrs_ctx_t *ctx, int num_keys, const sqlrs_order_by_t *o
       o->asc.push_back(order_by[i].asc);
     }
     o->limit_all_keys = num_keys > 0 && (order_by[0].reserved & SQLRS_ORDER_LIMIT_ALL_KEYS) != 0;
+    o->hstage.all_types = num_keys > 0 && stage_all_types_flag(1, &order_by[0].expr); // SQLRS_EXPR_STAGE_ALL_TYPES (host_stage.hpp)
     *out = o.release();
   });
 }
@@ -933,7 +934,8 @@ static int order_flush_host(sqlrs_order_t *o) {
 int sqlrs_order_push(sqlrs_order_t *o, const sqlrs_batch_t *in) {
   o->hstage.ctx = o->ctx;
   if (o->hstage.accepts(in)) {
-    int st = guard(o->ctx, [&] { o->hstage.append(in); });
+    int st = o->hstage.flush_before(in) ? order_flush_host(o) : SQLRS_OK;
+    if (st == SQLRS_OK) st = guard(o->ctx, [&] { o->hstage.append(in); });
     if (st != SQLRS_OK || o->hstage.rows < HOST_STAGE_FLUSH_ROWS) return st;
     return order_flush_host(o);
   }

@@ -148,8 +148,11 @@ class HashJoinExecutor:
                  join_type: str, join_condition: JoinCondition, join_output_schema: pa.Schema,
                  num_left_columns: int, out_mem: int = abi.MEM_HOST, many: int = 0, depth: int = 0,
                  async_general: bool = False, async_utf8: bool = False, async_filter: bool = False,
-                 async_keys: bool = False):
+                 async_keys: bool = False, stage_all_types: bool = False):
         self.backend = backend
+        # SQLRS_EXPR_STAGE_ALL_TYPES on the first build key: small HOST build batches with Utf8 / Boolean columns and NULLs are
+        # staged too (opt-in; a backend that does not stage — the oracle — ignores the field)
+        self.stage_all_types = stage_all_types
         self.depth = depth  # > 0: probe batches through sqlrs_hash_join_probe_push_async, that many tickets in flight
         # sqlrs_hash_join_set_async_general: with depth > 0, outer joins and duplicate build keys take one launch per batch too
         # (a backend without the entry point — the oracle — runs unchanged)
@@ -177,6 +180,8 @@ class HashJoinExecutor:
         lk, k1 = abi.pack_exprs([l for l, _ in self.join_condition.on])
         rk, k2 = abi.pack_exprs([r for _, r in self.join_condition.on])
         keep += [lk, rk, k1, k2]
+        if self.stage_all_types and k1:
+            lk[0].reserved = abi.EXPR_STAGE_ALL_TYPES
         filt = None
         if self.join_condition.filter is not None:
             pf = self.join_condition.filter.pack()
@@ -266,8 +271,12 @@ class HashAggExecutor:
 
     def __init__(self, backend: abi.Backend, agg_funcs: List[AggFunc], group_by: List[BoundExpr],
                  child: Iterable, out_mem: int = abi.MEM_HOST,
-                 output_names: Optional[Sequence[str]] = None, child_filter: Optional[BoundExpr] = None):
+                 output_names: Optional[Sequence[str]] = None, child_filter: Optional[BoundExpr] = None,
+                 stage_all_types: bool = False):
         self.backend, self.agg_funcs, self.group_by = backend, agg_funcs, group_by
+        # SQLRS_EXPR_STAGE_ALL_TYPES on the first GROUP BY key: small HOST batches with Utf8 / Boolean columns and NULLs are
+        # staged too (opt-in; a backend that does not stage — the oracle — ignores the field)
+        self.stage_all_types = stage_all_types
         self.child, self.out_mem, self.output_names = child, out_mem, output_names
         # FilterExecutor{expr = child_filter, child} directly below the operator (filter.rs:7-25), handed to the
         # library (sqlrs_hash_agg_set_filter; HIP library only): same result as wrapping `child` in a FilterExecutor
@@ -279,6 +288,8 @@ class HashAggExecutor:
         keep = []
         gb, k = abi.pack_exprs(self.group_by)
         keep += [gb, k]
+        if self.stage_all_types and k:
+            gb[0].reserved = abi.EXPR_STAGE_ALL_TYPES
         aggs = (abi.AggFunc * max(len(self.agg_funcs), 1))(
             *[a.abi_struct(keep) for a in self.agg_funcs])
         h = C.c_void_p()
@@ -311,8 +322,12 @@ class HashJoinAggExecutor:
     def __init__(self, backend: abi.Backend, left_child: Iterable, right_child: Iterable,
                  join_condition: JoinCondition, join_output_schema: pa.Schema, num_left_columns: int,
                  agg_funcs: List[AggFunc], group_by: List[BoundExpr], out_mem: int = abi.MEM_HOST,
-                 output_names: Optional[Sequence[str]] = None, probe_filter: Optional[BoundExpr] = None):
+                 output_names: Optional[Sequence[str]] = None, probe_filter: Optional[BoundExpr] = None,
+                 stage_all_types: bool = False):
         self.backend = backend
+        # SQLRS_EXPR_STAGE_ALL_TYPES on the first build key: both sides' small HOST batches with Utf8 / Boolean columns and
+        # NULLs are staged too (opt-in)
+        self.stage_all_types = stage_all_types
         # FilterExecutor{expr = probe_filter, child = right_child} directly below the probe side
         # (filter.rs:7-25): same result as wrapping right_child in a FilterExecutor
         self.probe_filter = probe_filter
@@ -332,6 +347,8 @@ class HashJoinAggExecutor:
         rk, k2 = abi.pack_exprs([r for _, r in self.join_condition.on])
         gb, k3 = abi.pack_exprs(self.group_by)
         keep += [lk, rk, gb, k1, k2, k3]
+        if self.stage_all_types and k1:
+            lk[0].reserved = abi.EXPR_STAGE_ALL_TYPES
         aggs = (abi.AggFunc * max(len(self.agg_funcs), 1))(*[a.abi_struct(keep) for a in self.agg_funcs])
         right_fields = list(self.join_output_schema)[self.num_left_columns:]
         rd = (C.c_int32 * max(len(right_fields), 1))(*[abi.dtype_of(f.type) for f in right_fields])
@@ -368,8 +385,11 @@ class OrderExecutor:
 
     def __init__(self, backend: abi.Backend, order_by: List[OrderBy], child: Iterable,
                  out_mem: int = abi.MEM_HOST, retain_inputs: bool = False, limit_hint: Optional[int] = None,
-                 limit_all_keys: bool = False):
+                 limit_all_keys: bool = False, stage_all_types: bool = False):
         self.backend, self.order_by, self.child, self.out_mem = backend, order_by, child, out_mem
+        # SQLRS_EXPR_STAGE_ALL_TYPES on the first key's expression: small HOST batches with Utf8 / Boolean columns and NULLs are
+        # staged too (opt-in; a backend that does not stage — the oracle — ignores the field)
+        self.stage_all_types = stage_all_types
         # SQLRS_ORDER_LIMIT_ALL_KEYS on the first key: the hint also serves a Utf8 / nullable / expression first key (opt-in;
         # only handed to a backend that takes the hint: the oracle runs unchanged)
         self.limit_all_keys = limit_all_keys
@@ -390,6 +410,8 @@ class OrderExecutor:
         hinted = self.limit_hint is not None and hasattr(be.lib, be.prefix + "order_set_limit")  # (HIP library only)
         if hinted and self.limit_all_keys and obs:
             obs[0].reserved = abi.ORDER_LIMIT_ALL_KEYS
+        if self.stage_all_types and obs:
+            obs[0].expr.reserved = abi.EXPR_STAGE_ALL_TYPES
         arr = (abi.OrderBy * max(len(obs), 1))(*obs)
         h = C.c_void_p()
         be.check(be.fn("order_create")(be.ctx, len(obs), arr, C.byref(h)))
