@@ -88,7 +88,7 @@ struct sqlrs_hash_join {
   bool lds_first = false;
   bool async_ordered = false; // the async path's side streams have been ordered behind this join's build (small_async.hpp)
   // sqlrs_hash_join_set_async_general: probe_push_async also takes outer joins and duplicate build keys in one launch per batch
-  // (sa_probe_general_kernel, join.hip).  `max_run` = M, the most build rows that share one key (0: not computed yet; rows with
+  // (sa_probe_general_kernel, join_async.hip).  `max_run` = M, the most build rows that share one key (0: not computed yet; rows with
   // a NULL key count as sharing one) — what bounds the rows a batch can emit; `probe_started`: a probe call of any kind was made
   bool async_general = false, probe_started = false;
   uint32_t max_run = 0;
@@ -96,7 +96,7 @@ struct sqlrs_hash_join {
   // build column c in bytes, NULL slots included (-1: not a Utf8 column), computed when the first batch needs it (utf8_lmax_known)
   bool async_utf8 = false, utf8_lmax_known = false;
   std::vector<int64_t> utf8_lmax;
-  // sqlrs_hash_join_set_async_filter: both async probe kernels evaluate the join filter on the joined row (sa_eval_row, join.hip).
+  // sqlrs_hash_join_set_async_filter: both async probe kernels evaluate the join filter on the joined row (sa_eval_row, join_async.hip).
   // The filter is compiled ONCE per join, over the build side's dtypes followed by `right_dtypes` (filter_prog_state: 0 not tried
   // yet, 1 compiled, -1 not expressible — such a join keeps the synchronous operator), and uploaded once (filter_prog: one
   // SaProgram in HBM, filter_prog_host the bytes it was copied from).  filter_pairs: the general kernel's list of kept
@@ -105,7 +105,7 @@ struct sqlrs_hash_join {
   int filter_prog_state = 0;
   std::vector<unsigned char> filter_prog_host;
   sq::BufP filter_prog, filter_pairs;
-  // sqlrs_hash_join_set_async_keys: both async probe kernels load the key of a probe row themselves (sa_probe_key, join.hip): NULL
+  // sqlrs_hash_join_set_async_keys: both async probe kernels load the key of a probe row themselves (sa_probe_key, join_async.hip): NULL
   // probe keys in exact mode, and the hashed key of a Utf8 key or of 2 .. 4 key columns (key_hash.hpp)
   bool async_keys = false;
 };
@@ -113,6 +113,13 @@ struct sqlrs_hash_join {
 // builds the deferred hash table of a `lazy_table` join (join.hip); no-op otherwise
 namespace sq {
 void hash_join_ensure_table(sqlrs_hash_join *j);
+// what the async probe (join_async.hip) calls in join.hip: the direct-address build's pending verdict -> the join's state (`h`:
+// the verdict's words when the caller has fetched them already), the direct-address table as the probe kernels take it
+// (join_table.hpp), and the synchronous operator for one probe batch, its joined rows as a HOST batch
+struct DenseTable;
+void dense_resolve(sqlrs_hash_join *j, const uint64_t *h = nullptr);
+DenseTable dense_table_of(const sqlrs_hash_join *j);
+sqlrs_batch_t *hash_join_probe_sync(sqlrs_hash_join *j, const sqlrs_batch_t *right);
 // existence bitmap of a direct-address (`dense`) join: bit (key - dense_min) is set when the key has a build row
 // (join.hip, dense_bits_kernel); built once, on first need
 const uint64_t *hash_join_dense_bits(sqlrs_hash_join *j);

@@ -1,5 +1,5 @@
 // key_hash.hpp — the arithmetic of a hashed join / group key (normalize_keys' hash mode, keys.hip), in ONE place: the fold_*
-// kernels of keys.hip fold a column at a time over device columns, the key loader of the one-launch probe kernels (join.hip,
+// kernels of keys.hip fold a column at a time over device columns, the key loader of the one-launch probe kernels (join_async.hip,
 // sa_probe_key) folds a row at a time over the columns staged in a pinned slot.  Both must produce the same 64 bits for the same
 // row — the build side's table is keyed by the former, a probe row is looked up by the latter.
 //   acc = 0; per key column, in order: a NULL leaves acc unchanged (hash_utils.rs:91-104), otherwise

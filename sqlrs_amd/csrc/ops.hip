@@ -325,12 +325,6 @@ __global__ __launch_bounds__(1024) void sa_filter_kernel(SaGroup<SaFilterParams>
   }
   sa_publish((SaHeader *)p.out, p.seq, total, s_nulls, p.lay.ncols, &s_div0);
 }
-template <bool WIDE> static void sa_filter_launch(SaRing *r, Ctx *ctx) { // (a group is of ONE launch function: sa_enqueue)
-  SaGroup<SaFilterParams> g;
-  for (int i = 0; i < r->pend_n; i++) std::memcpy(&g.p[i], r->pend_buf + (size_t)i * SA_PARAM_MAX, sizeof(SaFilterParams));
-  sa_filter_kernel<WIDE><<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g); // (reads nothing the ctx stream produces)
-  SQ_HIP(hipGetLastError());
-}
 // the shapes the fast path evaluates: t1 [t2 AND [t3 AND [t4 AND]]] in postfix, every term INPUT_REF CONSTANT CMP over an
 // int32 / int64 / float64 column with a constant of the column's type
 static bool sa_filter_term(const sqlrs_expr_node_t *nd, const sqlrs_batch_t *in, int *pred_col, int *is32, RowFilter *rf) {
@@ -388,10 +382,9 @@ int sqlrs_filter_push_async(sqlrs_filter_t *f, const sqlrs_batch_t *in, sqlrs_ti
     auto t = std::unique_ptr<sqlrs_ticket>(new sqlrs_ticket());
     t->ctx = ctx;
     SaFilterParams p;
-    const char *off_e = hook("SQLRS_ASYNC_FAST"); // test hook, read per call: 0 = every batch through the synchronous operator
     const bool all_types = f->async_all_types;
     SaPool pool;
-    if (!(off_e && off_e[0] == '0') && (sa_filter_shape(f->expr, in, &p) || sa_filter_program(f->expr, in, &p, all_types, &pool))) {
+    if (!sa_fast_off() && (sa_filter_shape(f->expr, in, &p) || sa_filter_program(f->expr, in, &p, all_types, &pool))) {
       SaRing *r = sa_ring(ctx);
       const int slot = r ? sa_take_slot(r) : -1;
       if (slot >= 0) {
@@ -408,7 +401,7 @@ int sqlrs_filter_push_async(sqlrs_filter_t *f, const sqlrs_batch_t *in, sqlrs_ti
           p.in = r->in_area(slot);
           p.out = r->out_area(slot);
           p.seq = ++r->seq;
-          sa_enqueue(ctx, r, f, wide ? sa_filter_launch<true> : sa_filter_launch<false>, p, slot);
+          sa_enqueue(ctx, r, f, wide ? sa_launch_group<SaFilterParams, sa_filter_kernel<true>> : sa_launch_group<SaFilterParams, sa_filter_kernel<false>>, p, slot);
           if (p.nterms) ctx->async_conj_batches++; // (sa_filter_shape took it: the program counts in async_fast_batches alone)
           t->slot = slot;
           t->seq = p.seq;

@@ -298,12 +298,6 @@ __global__ __launch_bounds__(1024) void sa_project_kernel(SaGroup<SaProjectParam
   }
   sa_publish((SaHeader *)p.out, p.seq, rows, s_nulls, p.nout, &s_div0);
 }
-template <bool WIDE> static void sa_project_launch(SaRing *r, Ctx *ctx) {
-  SaGroup<SaProjectParams> g;
-  for (int i = 0; i < r->pend_n; i++) std::memcpy(&g.p[i], r->pend_buf + (size_t)i * SA_PARAM_MAX, sizeof(SaProjectParams));
-  sa_project_kernel<WIDE><<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g); // (reads nothing the ctx stream produces)
-  SQ_HIP(hipGetLastError());
-}
 // plans the batch (which columns are copied, which computed), lays it out in the slot and copies what the host copies;
 // false: not a batch for the fast path
 static bool sa_project_stage(const sqlrs_project *pj, const sqlrs_batch_t *in, uint8_t *in_area, uint8_t *out_area, SaProjectParams *pp,
@@ -479,8 +473,7 @@ int sqlrs_project_push_async(sqlrs_project_t *p, const sqlrs_batch_t *in, sqlrs_
     SQ_HIP(hipSetDevice(ctx->device));
     auto t = std::unique_ptr<sqlrs_ticket>(new sqlrs_ticket());
     t->ctx = ctx;
-    const char *off_e = hook("SQLRS_ASYNC_FAST"); // test hook, read per call: 0 = every batch through the synchronous operator
-    if (!(off_e && off_e[0] == '0')) {
+    if (!sa_fast_off()) {
       SaRing *r = sa_ring(ctx);
       const int slot = r ? sa_take_slot(r) : -1;
       if (slot >= 0) {
@@ -489,7 +482,7 @@ int sqlrs_project_push_async(sqlrs_project_t *p, const sqlrs_batch_t *in, sqlrs_
           pp.in = r->in_area(slot);
           pp.out = r->out_area(slot);
           pp.seq = ++r->seq;
-          sa_enqueue(ctx, r, p, pp.wide ? sa_project_launch<true> : sa_project_launch<false>, pp, slot);
+          sa_enqueue(ctx, r, p, pp.wide ? sa_launch_group<SaProjectParams, sa_project_kernel<true>> : sa_launch_group<SaProjectParams, sa_project_kernel<false>>, pp, slot);
           t->slot = slot;
           t->seq = pp.seq;
           *ticket = t.release();

@@ -1,50 +1,48 @@
-// small_async.hpp — the reference's calling shape without a stream synchronisation per call (round 6, review r05 #6).
+// small_async.hpp — push_async: the reference's calling shape, ONE 1024-row HOST batch per poll (storage/csv.rs:105,
+// filter.rs:15-24, hash_join.rs:284-291), without a stream synchronisation per call (round 6, review r05 #6).
 //
-// The reference polls ONE 1024-row batch at a time (storage/csv.rs:105, filter.rs:15-24, hash_join.rs:284-291).  A
-// synchronous `push` of such a batch is a chain of round trips — upload, two to four launches, the count, the download, a
-// stream synchronisation: ~47 us for 8 KB of rows, 21 Mrows/s (Filter) / 11 Mrows/s (HashJoin probe).  `push_async` hands
-// back a TICKET instead of a batch and `sqlrs_batch_wait(ticket)` the batch; a caller that waits one (or a few) batches
-// behind never blocks on the device.  The fast path is ONE launch per batch and no copy call at all:
-//   * the batch's columns are copied (memcpy, 8 KB per column) into a slot of a pinned, device-mapped ring;
-//   * one 1024-thread workgroup reads them over PCIe, evaluates the predicate — a conjunction of `column OP constant` terms directly, anything else over the
-//     int32 / int64 / float64 columns as a postfix program (SaProgram, sa_eval_row: the evaluator's semantics row by row) — or looks the keys up in the
-//     join's table (HashJoin, unique build keys), compacts the kept rows with ballots, gathers the build columns, and
-//     writes the output columns + validity bitmaps + a header {sequence number, rows, NULL counts} back into the slot;
-//   * `wait` polls the header's sequence number (system-scope release store behind `__threadfence_system`), falling
+// Mechanism.  A synchronous `push` of such a batch is a chain of round trips — upload, two to four launches, the count, the
+// download, a stream synchronisation: ~47 us for 8 KB of rows, 21 Mrows/s (Filter) / 11 Mrows/s (HashJoin probe).  `push_async`
+// hands back a TICKET and `sqlrs_batch_wait(ticket)` the batch; a caller that waits a few batches behind never blocks on the
+// device.  The fast path is ONE launch per batch and no copy call at all:
+//   * the batch's columns are copied (memcpy, 8 KB per column) into a slot of a pinned, device-mapped ring (sa_stage_input);
+//   * one 1024-thread workgroup reads them over PCIe and does the operator's work.  Filter: the predicate — a conjunction of
+//     `column OP constant` terms directly, anything else as a postfix program (SaProgram, sa_eval_row: the evaluator's semantics
+//     row by row) — and the kept rows of every column compacted with ballots (sa_positions).  Project: a
+//     program per computed column.  HashJoin probe: one lookup per row in the join's table, the build columns gathered;
+//   * it writes the output columns + validity bitmaps + a header {sequence number, rows, NULL counts} back into the slot
+//     (sa_publish); `wait` polls the header's sequence number (a system-scope release store behind __threadfence_system), falls
 //     back to a stream synchronisation when it does not show up, and copies the rows into an ordinary HOST batch.
-// Anything the fast path does not take — predicates that read a Boolean / Utf8 column (unless the operator's all-types switch is
-// on, last paragraph but one), a batch that carries a Boolean column (the same switch), predicates of more than 24 nodes, Utf8
-// columns around a join (unless the join's Utf8 switch is on, below), more than 4096 rows, DEVICE input, join filters (unless the join's filter switch is on, below), NULL probe keys and Utf8 / multi-column join keys (unless the join's key switch is on, below), Boolean keys, the opt-in composite key,
-// duplicate build keys and outer joins (unless the join's switch is on, next paragraph) — runs the synchronous operator
-// inside push_async and parks the finished batch in the ticket: same results, same one-output-per-input rule, no speed-up.
-// sqlrs_hash_join_set_async_general(j, 1): Left / Right / Full joins and build sides with duplicate keys take ONE launch per
-// batch as well (sa_probe_general_kernel, join.hip) — a batch of `rows` rows against a build side whose most frequent key
-// has M rows emits at most rows x M joined rows, and it is taken when rows x M <= SA_MAX_OUT_ROWS and the output columns
-// laid out for rows x M rows fit the slot's output area; the host decides before it takes a slot, nothing overflows.
-// sqlrs_hash_join_set_async_utf8(j, 1): both probe kernels also carry Utf8 PAYLOAD columns, build side and probe side (the key
-// stays int32 / int64 / float64): sa_probe_kernel<true> with the Filter's scheme (lengths by output position in LDS, a block scan,
-// a byte copy per row), sa_probe_general_kernel<true> with a scan per 1024-row chunk of output and a running byte base per
-// column.  The host reserves out_rows x Lmax bytes for a build column (Lmax: its longest string, NULL slots included, one kernel
-// and one fetch per join) and B x (out_rows / rows) for a probe column of B bytes, and admits the batch only when that fits the
-// slot; the kernels check every column's bytes against SaCol::out_cap before they store one.
-// sqlrs_hash_join_set_async_filter(j, 1): both probe kernels also serve a join WITH a join filter (FILTER = true instantiations):
-// the filter is compiled once per join into an SaProgram over the joined schema (sa_compile over a dtype list), uploaded once,
-// copied into LDS at kernel start and evaluated by sa_eval_row through a joined-row operand loader (build columns from HBM,
-// probe columns from the slot).  sa_probe_kernel keeps a matched row iff the filter is valid and TRUE; sa_probe_general_kernel
-// evaluates it per candidate, compacts the kept candidates into a list in HBM (a region per ring slot), appends the Right / Full
-// probe rows that kept none, and emits from the list — apply_join_filter's order and its visited marks; a valid candidate that
-// divides by zero is SaHeader::pad = 1, the evaluator's error at the wait.  The output bound is the unfiltered one (candidates).
-// sqlrs_hash_join_set_async_keys(j, 1): both probe kernels load the key of a probe row themselves (the KEYS instantiations, sa_probe_key,
-// join.hip): a NULL key of an exactly compared key takes the NULL build rows, a Utf8 key or a key of 2 - 4 columns is the u64 that
-// normalize_keys computes (key_hash.hpp: one definition for the fold_* kernels and the loader), looked up as a value: match-by-hash.
-// sqlrs_filter_set_async_all_types(f, 1) / sqlrs_project_set_async_all_types(p, 1): the program also reads Utf8 and Boolean columns
-// (sa_compile with `wide`, sa_eval_row<true>, SaSlotLoadWide: the `wide` instantiations of sa_filter_kernel / sa_project_kernel, chosen
-// per batch — a batch with nothing wide in it keeps the narrow kernel).  A Utf8 value is ONE stack word {length, byte offset in the slot's
-// input area}: a column's from its staged offsets, a constant's from a pool of at most SA_POOL_MAX bytes per expression that the host stages
-// behind the columns; the six comparisons read both operands' bytes from the slot (cmp_utf8_kernel's order: unsigned bytes, a prefix is
-// less).  A Boolean column is bit r of its staged value bitmap: an operand of comparisons, AND / OR and casts, or the predicate itself.
-// The Filter compacts a Boolean payload column like a validity bitmap (sa_pack_bits).  With the switch on only SIZE sends a HOST batch to
-// the synchronous operator: rows, columns, nodes, stack depth, pool bytes, slot bytes.  (A join's filter keeps the narrow program.)
+// Up to SA_GROUP_MAX consecutive batches of one operator leave with one launch (sa_enqueue, sa_launch_group), on SA_STREAMS side streams.
+// Without a switch the path takes batches of int32 / int64 / float64 columns (the Filter: Utf8 payload columns too) and programs
+// over them; the join: Inner, unique build keys, ONE exactly compared key column without a NULL in the batch, no join filter.
+//
+// Switches (off by default; the join's are set before its first probe call), what each admits, and the kernel that serves it:
+//   sqlrs_hash_join_set_async_general   Left / Right / Full joins and duplicate build keys.  A batch of `rows` rows against a
+//     sa_probe_general_kernel           build side whose most frequent key has M rows emits <= rows x M rows: taken when that
+//                                       is <= SA_MAX_OUT_ROWS and the output laid out for it fits the slot — the host decides
+//                                       before it takes a slot, nothing overflows.
+//   sqlrs_hash_join_set_async_utf8      Utf8 PAYLOAD columns on both sides of the join.  The host reserves out_rows x Lmax bytes
+//     UTF8 = true of both probe         for a build column (Lmax: its longest string, one kernel and one fetch per join) and
+//     kernels                           B x (out_rows / rows) for a probe column of B bytes, admits the batch when that fits;
+//                                       the kernels check a column's bytes against SaCol::out_cap before they store one.
+//   sqlrs_hash_join_set_async_filter    a join WITH a join filter: compiled once per join into an SaProgram over the joined
+//     FILTER = true of both             schema, uploaded once, copied into LDS at kernel start, evaluated on the joined row
+//                                       (build columns from HBM, probe columns from the slot).  sa_probe_kernel keeps a pair
+//                                       iff the filter is valid and TRUE; sa_probe_general_kernel follows apply_join_filter
+//                                       (kept candidates as a list in HBM, then the Right / Full rows that kept none).  A
+//                                       valid candidate that divides by zero: SaHeader::pad = 1, the evaluator's error at the wait.
+//   sqlrs_hash_join_set_async_keys      NULL probe keys (they take the NULL build rows), a Utf8 key (with the Utf8 switch), 2 - 4
+//     KEYS = true of both (only with    key columns: the kernel loads a row's key itself (sa_probe_key), the hashed forms as the
+//     UTF8 = true)                      u64 normalize_keys computes (key_hash.hpp), looked up as a value: match-by-hash.
+//   sqlrs_filter_set_async_all_types    programs that read Utf8 / Boolean columns and Utf8 constants (sa_compile with `wide`,
+//   sqlrs_project_set_async_all_types   SaSlotLoadWide; constants in a pool of <= SA_POOL_MAX bytes staged behind the columns),
+//     WIDE = true of sa_filter_kernel   Boolean payload columns (compacted like a validity bitmap, sa_pack_bits).  Chosen per
+//     / sa_project_kernel               batch: one with nothing wide in it keeps the narrow kernel.  A join's filter stays narrow.
+//
+// Everything else — DEVICE input, more than SA_MAX_ROWS rows or SA_MAX_COLS columns, a program past SA_PROG_MAX nodes / SA_STACK_MAX
+// stack words, Boolean join keys, the opt-in composite key, a batch that does not fit its slot, no free slot — runs the synchronous
+// operator inside push_async and parks the finished batch in the ticket: same results, one output per input, no speed-up.
 #pragma once
 
 #include <cstring>
@@ -184,6 +182,10 @@ inline void sa_place_pool(SaProgram *pr, uint32_t pool_off) {
   for (int k = 0; k < pr->n; k++)
     if (pr->ins[k].op == SAO_CONST && pr->ins[k].dtype == SQLRS_UTF8) pr->ins[k].imm += pool_off;
 }
+inline bool sa_fast_off() {
+  const char *e = hook("SQLRS_ASYNC_FAST"); // test hook, read per call: 0 = every batch through the synchronous operator
+  return e && e[0] == '0';
+}
 
 } // namespace sq
 
@@ -241,7 +243,7 @@ __device__ __forceinline__ void sa_cmp_utf8(const uint8_t *base, unsigned long l
   *eq = c == 0;
 }
 // one row of the program: *valid = the result is not NULL; *div0 raised when a valid row divides by zero.  `load(column, &ok)`
-// fetches an operand: SaSlotLoad for the Filter / Project kernels, the joined-row loader of the probe kernels (join.hip).
+// fetches an operand: SaSlotLoad for the Filter / Project kernels, the joined-row loader of the probe kernels (join_async.hip).
 // WIDE (a compile-time flag: the other instantiations keep their code): Utf8 comparisons, through load.bytes() (SaSlotLoadWide)
 template <bool WIDE = false, class Load>
 __device__ __forceinline__ unsigned long long sa_eval_row(const SaProgram &pr, const Load &load, bool *valid, bool *div0) {
@@ -347,11 +349,28 @@ __device__ __forceinline__ unsigned long long sa_eval_row(const SaProgram &pr, c
   return sa_eval_row(pr, SaSlotLoad{lay, in, r}, valid, div0);
 }
 
+// The block step of a scan over the 16 waves of ONE 1024-thread workgroup: the lane that holds its wave's total (`owner`: lane 0
+// behind a ballot, lane 63 behind wave_iscan_u32) stores it into s_w[wave]; *before = the totals of the waves in front of this
+// one, *all = those of all 16.  The ONE barrier is between the store and the loads: the caller places the barrier that lets s_w
+// be written again.  `s_w`: 16 words of LDS.
+__device__ __forceinline__ void sa_block_prefix(uint32_t *s_w, bool owner, uint32_t wave_total, uint32_t *before, uint32_t *all) {
+  const int w = wave_id();
+  if (owner) s_w[w] = wave_total;
+  __syncthreads();
+  uint32_t b = 0, a = 0;
+#pragma unroll
+  for (int q = 0; q < 16; q++) {
+    const uint32_t c = s_w[q];
+    b += q < w ? c : 0;
+    a += c;
+  }
+  *before = b;
+  *all = a;
+}
 // Output positions of the kept rows of <= 4096 rows on ONE 1024-thread workgroup: pos[t] for row t * 1024 + tid, bit t of
 // the return value = kept; *total = kept rows.  `s_w`: 17 words of LDS.
 template <class KeepFn>
 __device__ __forceinline__ uint32_t sa_positions(uint32_t rows, KeepFn keep_of, uint32_t (&pos)[4], uint32_t *s_w, uint32_t *total) {
-  const int lane = lane_id(), w = wave_id();
   uint32_t base = 0, bits = 0;
 #pragma unroll
   for (int t = 0; t < 4; t++) {
@@ -359,15 +378,8 @@ __device__ __forceinline__ uint32_t sa_positions(uint32_t rows, KeepFn keep_of, 
     const uint32_t r = (uint32_t)t * 1024u + threadIdx.x;
     const bool k = r < rows && keep_of(r, t);
     const uint64_t bm = __ballot(k);
-    if (lane == 0) s_w[w] = (uint32_t)__popcll(bm);
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int q = 0; q < 16; q++) {
-      const uint32_t c = s_w[q];
-      before += q < w ? c : 0;
-      all += c;
-    }
+    uint32_t before, all;
+    sa_block_prefix(s_w, lane_id() == 0, (uint32_t)__popcll(bm), &before, &all);
     pos[t] = base + before + mbcnt(bm);
     bits |= k ? 1u << t : 0u;
     base += all;
@@ -408,6 +420,26 @@ __device__ __forceinline__ void sa_pack_bits(const uint8_t *s_v, uint32_t total,
     out_bits[i] = (uint8_t)byte;
   }
   __syncthreads();
+}
+// the probe row of output row `o` of a batch whose row r emits the rows [s_off[r], s_off[r + 1]): the last of the `rows` probe
+// rows whose first output row is <= o (s_off[0] = 0)
+__device__ __forceinline__ uint32_t sa_output_row(const uint32_t *s_off, uint32_t rows, uint32_t o) {
+  uint32_t lo = 0, hi = rows;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (s_off[mid] <= o) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+// The launch function of a kernel over SaGroup<P> for sa_enqueue: the pending parameters, one workgroup per batch, on the side
+// stream of the group's first slot.  One function address per kernel instantiation, which is how sa_enqueue tells groups apart.
+template <class P, auto Kernel> void sa_launch_group(SaRing *r, Ctx *ctx) {
+  static_assert(sizeof(P) <= SA_PARAM_MAX, "parameter block too large");
+  SaGroup<P> g;
+  for (int i = 0; i < r->pend_n; i++) std::memcpy(&g.p[i], r->pend_buf + (size_t)i * SA_PARAM_MAX, sizeof(P));
+  Kernel<<<dim3((unsigned)r->pend_n), dim3(1024), 0, r->stream_of(r->pend_first_slot)>>>(g);
+  SQ_HIP(hipGetLastError());
 }
 // the last step of a fast-path kernel: every thread's stores to the pinned output are pushed out, then ONE thread
 // publishes the header.  `s_error` (LDS, may be null) is read BEHIND the barrier like `s_nulls`: any wave may have raised it

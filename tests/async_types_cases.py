@@ -182,6 +182,17 @@ def stream():
     return bs
 
 
+@_cached
+def adjacent_utf8_stream():
+    """(s utf8, t utf8, rid int64) at 65 and 1025 rows, NO NULL in either Utf8 column: the one shape in which the Filter goes from
+    one Utf8 column's byte copy to the next column's lengths through the bare `else __syncthreads()` and not through the barriers
+    of a bitmap pass.  It pins that route's RESULT; it cannot tell whether that barrier is there (a thread's first stores into the
+    lengths go to the entries it read itself, and the scan's stores come behind the next column's own first barrier)"""
+    rng = np.random.default_rng(211)
+    return [pa.RecordBatch.from_arrays([_strings(rng, rows, VOCAB, 0.0), _strings(rng, rows, VOCAB, 0.0, shift=5), pa.array(np.arange(rows, dtype=np.int64))],
+                                       names=["s", "t", "rid"]) for rows in (65, 1025)]
+
+
 def stream_predicates():
     s, t, a, p, q = InputRef(S), InputRef(T), InputRef(A), InputRef(P), InputRef(Q)
     u = lambda v: Constant(v, abi.UTF8)  # noqa: E731

@@ -243,8 +243,24 @@ def bound_case():
     return Case("bound", lb, rbs, 0, 0, [(jt, g) for jt in JOIN_TYPES for g in (False, True) if g or jt == "inner"])
 
 
+@_cached
+def adjacent_case():
+    """Inner / unique route: two ADJACENT Utf8 columns without a NULL on the build side, and two on the probe side, at 65 and
+    1025 rows — the one shape in which sa_probe_kernel<true> goes from one Utf8 column's byte copy to the next column's lengths
+    through the bare `else __syncthreads()` and not through the barriers of a bitmap pass.  It pins that route's RESULT, for build
+    rows and for probe rows; it cannot tell whether that barrier is there (a thread's first stores into the lengths go to the
+    entries it read itself, the scan's come behind the next column's first barrier); a 5000-row batch is synchronous"""
+    rng = np.random.default_rng(53)
+    nb = 1500
+    lb = pa.RecordBatch.from_arrays([pa.array(rng.permutation(2000)[:nb].astype(np.int64)), str_array(rand_strings(rng, nb)), str_array(rand_strings(rng, nb, 2))],
+                                    names=["k", "s1", "s2"])
+    rbs = [pa.RecordBatch.from_arrays([pa.array(rng.integers(0, 2000, rows)), str_array(rand_strings(rng, rows)), str_array(rand_strings(rng, rows, 2), None, shift=3)],
+                                      names=["k", "t1", "t2"]) for rows in (65, 1025, 5000)]
+    return Case("adjacent_utf8", lb, rbs, 0, 0, [("inner", False)])
+
+
 def all_cases():
-    return [form_case(f) for f in FORMS] + [chunk_case(), empty_strings_case(), bound_case()]
+    return [form_case(f) for f in FORMS] + [chunk_case(), empty_strings_case(), bound_case(), adjacent_case()]
 
 
 # ---- the fuzz ---------------------------------------------------------------------------------------------------------

@@ -139,6 +139,20 @@ def test_sliced_utf8_input(hip, oracle):
         assert M.column_values(got.column(1)) == M.column_values(b.column(0)) and M.column_values(got.column(2)) == M.column_values(b.column(1))
 
 
+def test_adjacent_utf8_columns_without_nulls(hip, oracle):
+    """sa_filter_kernel, 65 and 1025 rows: two Utf8 payload columns side by side, neither with a NULL (tests/async_types_cases.py,
+    adjacent_utf8_stream: the route from one Utf8 column to the next without a bitmap pass between them), narrow and wide kernel"""
+    bs = K.adjacent_utf8_stream()
+    assert all(c.null_count == 0 for b in bs for c in b.columns) and [b.num_rows for b in bs] == [65, 1025]
+    for label, e in (("rid % 3", (InputRef(2) - (InputRef(2) / Constant(3, abi.INT64)) * Constant(3, abi.INT64)) > Constant(0, abi.INT64)), ("s >= t", InputRef(0) >= InputRef(1))):
+        with route(hip, len(bs)):
+            got = list(FilterExecutor(hip, e, bs, depth=1, async_all_types=True).execute())
+        assert all(0 < g.num_rows < b.num_rows for g, b in zip(got, bs)), label
+        sync, orc = sync_and_oracle(hip, oracle, ("adjacent", label), lambda be: FilterExecutor(be, e, bs))
+        K.same_batches(got, sync, label + " against push")
+        K.same_batches(got, orc, label + " against the oracle")
+
+
 def test_all_rows_kept(hip):
     """4096 rows kept whole with Boolean and Utf8 payload: the last word of the compacted bitmaps and the end offset"""
     rng = np.random.default_rng(9)

@@ -1,6 +1,6 @@
 """sqlrs_hash_join_set_async_filter: a join WITH a join filter through ONE launch per probe batch of
 sqlrs_hash_join_probe_push_async — the filter evaluated on the joined row inside sa_probe_kernel<., true> /
-sa_probe_general_kernel<., true> (csrc/join.hip) with apply_join_filter's semantics.  The async stream must be the synchronous
+sa_probe_general_kernel<., true> (csrc/join_async.hip) with apply_join_filter's semantics.  The async stream must be the synchronous
 stream and the oracle's, batch for batch, the tail batch of Left / Full included; which batches take a kernel is the rule of
 include/sqlrs_hip.h, restated in tests/async_filter_cases.py."""
 import ctypes as C

@@ -1,5 +1,5 @@
 """sqlrs_hash_join_set_async_general: Left / Right / Full joins and build sides with duplicate keys through ONE launch per probe
-batch of sqlrs_hash_join_probe_push_async (sa_probe_general_kernel, csrc/join.hip).  The async stream must be the synchronous
+batch of sqlrs_hash_join_probe_push_async (sa_probe_general_kernel, csrc/join_async.hip).  The async stream must be the synchronous
 stream and the oracle's, batch for batch, the tail batch of Left / Full included; which batches take the kernel is the rule of
 include/sqlrs_hip.h, restated here from the batch, the build side's true M and the header's constants."""
 import ctypes as C

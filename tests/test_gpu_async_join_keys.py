@@ -1,5 +1,5 @@
 """sqlrs_hash_join_set_async_keys: NULL probe keys, Utf8 keys and keys of 2 to 4 columns through both one-launch kernels of
-sqlrs_hash_join_probe_push_async (the KEYS instantiations of sa_probe_kernel / sa_probe_general_kernel, sa_probe_key, csrc/join.hip).
+sqlrs_hash_join_probe_push_async (the KEYS instantiations of sa_probe_kernel / sa_probe_general_kernel, sa_probe_key, csrc/join_async.hip).
 The async stream must be the synchronous stream and the oracle's, batch for batch (exact Arrow equality), the tail batch of Left /
 Full included; which batches take a kernel is the rule of include/sqlrs_hip.h as tests/async_keys_cases.py restates it, and the
 counts it gives are the ones worked out by hand there.  With the switch off the count is what it was."""

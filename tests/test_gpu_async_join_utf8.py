@@ -1,5 +1,5 @@
 """sqlrs_hash_join_set_async_utf8: Utf8 payload columns, build side and probe side, through both one-launch kernels of
-sqlrs_hash_join_probe_push_async (sa_probe_kernel<true>, sa_probe_general_kernel<true>, csrc/join.hip).  The async stream must be
+sqlrs_hash_join_probe_push_async (sa_probe_kernel<true>, sa_probe_general_kernel<true>, csrc/join_async.hip).  The async stream must be
 the synchronous stream and the oracle's, batch for batch (exact Arrow equality), the tail batch of Left / Full included; which
 batches take a kernel is the rule of include/sqlrs_hip.h as tests/async_utf8_cases.py restates it."""
 import ctypes as C
@@ -84,6 +84,14 @@ def test_empty_and_all_null_string_columns(hip, oracle, jt):
     case = cases.empty_strings_case()
     for general in (True, False):
         check_case(hip, oracle, case, jt, 3, general)
+
+
+def test_adjacent_utf8_columns_without_nulls(hip, oracle):
+    """sa_probe_kernel<true>, 65 and 1025 rows: two Utf8 build columns and two Utf8 probe columns side by side, none with a NULL
+    (tests/async_utf8_cases.py, adjacent_case: the route from one Utf8 column to the next without a bitmap pass between them)"""
+    case = cases.adjacent_case()
+    assert all(c.null_count == 0 for b in [case.lb] + case.rbs for c in b.columns) and [b.num_rows for b in case.rbs[:2]] == [65, 1025]
+    check_case(hip, oracle, case, "inner", 1, False)
 
 
 @pytest.mark.parametrize("jt", ["inner", "right"])

@@ -7,7 +7,7 @@ own boundaries (64, JAP_ROWS 512, LJ_RANGE 2^15, the all-hit threshold 2^16).  I
 exactly (join_model.compare: validity bit for bit, values through integer views, Utf8 by value).
 
 Which route ran is asserted, not assumed: every run sits in a `route(...)` block over the counters of sqlrs_ctx_profile_read.
-`Plan` below restates the host-side dispatch of join.hip / join_lds.hip from the case's facts (rows, NULL keys, key range,
+`Plan` below restates the host-side dispatch of join.hip / join_async.hip / join_lds.hip from the case's facts (rows, NULL keys, key range,
 uniqueness), the join type, the hooks and the probe batches, and the block asserts that every `join_*` counter moved by exactly
 the planned number, that `async_fast_batches` did, and that every listed profile scope moved or stayed at rest as planned
 (DESIGN.md, "Route witnesses of the join"):
@@ -286,7 +286,7 @@ class Plan:
             self.scopes.add("join_probe_fill")
 
     def async_probe(self):
-        """a batch the one-launch kernels take: the table it reads is there (sa_probe_try / sa_probe_general_try)"""
+        """a batch the one-launch kernels take: the table it reads is there (sa_probe_try / sa_probe_general_try, csrc/join_async.hip)"""
         self.resolve()
         if not self.dense:
             self.ensure_table()
