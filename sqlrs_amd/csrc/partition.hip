@@ -234,11 +234,15 @@ extern "C" int sqlrs_hash_partition(sqlrs_ctx_t *ctx, const sqlrs_batch_t *in, c
     int64_t n1 = std::max<int64_t>(n, 1);
     BufP pid = ctx->alloc(8 * (size_t)n1), perm = ctx->alloc(4 * (size_t)n1);
     BufP counts = ctx->alloc_zero(8 * 256);
+    // NULL keys go to partition 0.  normalize_keys hands out the validity only in exact mode; in hash mode (a Utf8 key) a NULL
+    // key's hash stays 0 and would be placed like the value 0, part_of(0, parts): the key column's own validity says which rows
+    const uint64_t *kvalid = nk.validity;
+    if (!nk.exact && kc[0].validity && kc[0].null_count != 0) kvalid = kc[0].validity;
     if (n) {
       ProfScope ps(ctx, "hash_partition");
       unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(n, BLOCK), 4096);
       part_ids_kernel<<<dim3(blocks), dim3(BLOCK), 0, ctx->stream>>>(
-          nk.keys->as<uint64_t>(), nk.validity, n, (uint32_t)num_parts, pid->as<uint64_t>(),
+          nk.keys->as<uint64_t>(), kvalid, n, (uint32_t)num_parts, pid->as<uint64_t>(),
           counts->as<unsigned long long>());
       SQ_HIP(hipGetLastError());
       iota_u32(ctx, perm->as<uint32_t>(), n);
