@@ -10,7 +10,10 @@
  * Data model = Arrow column buffers, passed as plain pointers + sizes:
  *   - fixed-width columns: `values` = length * sizeof(T) little-endian
  *   - BOOLEAN columns:     `values` = Arrow bitmap (LSB-first), ceil(length/8) B
- *   - UTF8 columns:        `values` = bytes, `offsets` = (length+1) int32
+ *   - UTF8 columns:        `values` = bytes, `offsets` = (length+1) int32, non-decreasing; offsets[0] need not
+ *                            be 0, for HOST and DEVICE columns alike: the column is the rows it describes
+ *                            (bytes [offsets[0], offsets[length]) of `values`), so `offsets` may point into
+ *                            the offsets of a longer array.  Batches the library returns have offsets[0] = 0.
  *   - `validity`           = Arrow validity bitmap (LSB-first) or NULL (= all
  *                            valid); array offset must be 0 (slice on the host)
  *   - `mem`                = where the three pointers live (host or HBM)
@@ -95,6 +98,11 @@ typedef struct sqlrs_column {
  *     sqlrs_ctx_synchronize, or sqlrs_ctx_release_to_stream(ctx, s) before stream s reuses / frees them.
  *     (A stream-ordered allocator on another stream — e.g. torch's caching allocator — may hand a freed
  *     block to later work of ITS stream: order that stream behind the ctx with release_to_stream.)
+ *   - A DEVICE column may describe a window of a longer device array: `values` / `validity` advanced to the
+ *     window's first row (bitmaps by whole 8-byte words, i.e. a multiple of 64 rows), UTF8 `offsets` advanced
+ *     with `values` unchanged.  The library re-bases such offsets on the ctx stream and reads the bytes from
+ *     offsets[0] on; both ends of the offsets are fetched under the one synchronisation a DEVICE UTF8 column
+ *     already costs.
  *   - Device bitmaps (validity, BOOLEAN values) must be 8-byte aligned and readable up to the next multiple
  *     of 8 bytes (kernels read whole 64-bit words); host bitmaps have no such requirement.
  * Size limit, the same for every operator: 0 <= num_rows < 2^31 per batch (row ids travel as 32-bit words); a batch

@@ -313,19 +313,32 @@ DCol upload_column(Ctx *ctx, const sqlrs_column_t &c, bool force_copy) {
     break;
   case SQLRS_UTF8: {
     if (!c.offsets) fail(SQLRS_ERR_ARROW, "utf8 column without offsets");
-    int32_t last = 0;
-    if (c.mem == SQLRS_MEM_HOST)
+    int32_t last = 0, first = 0;
+    if (c.mem == SQLRS_MEM_HOST) {
       last = c.offsets[c.length];
-    else {
+      first = c.offsets[0];
+    } else { // (both ends of a DEVICE column's offsets under the one synchronisation)
       SQ_HIP(hipMemcpyAsync(&last, c.offsets + c.length, 4, hipMemcpyDeviceToHost, ctx->stream));
+      if (c.length > 0) SQ_HIP(hipMemcpyAsync(&first, c.offsets, 4, hipMemcpyDeviceToHost, ctx->stream));
       ctx->sync();
+      if (c.length == 0) first = last;
     }
     d.data_bytes = last;
-    // a HOST column whose offsets are a window into a longer array (offsets[0] = first != 0) is uploaded as the column it
-    // describes — the bytes [first, last), offsets from 0: concat_columns puts one part's bytes right behind the other's, and the
-    // bytes below `first` would land inside the last string of the part in front
-    const int32_t first = (c.mem == SQLRS_MEM_HOST && copy) ? c.offsets[0] : 0;
-    if (first > 0 && first <= last) {
+    // a column whose offsets are a window into a longer array (offsets[0] = first != 0), HOST or DEVICE, is taken as the column
+    // it describes — the bytes [first, last), offsets from 0: concat_columns puts one part's bytes right behind the other's, and the
+    // bytes below `first` would land inside the last string of the part in front (and an emitted batch would start at offsets[0]
+    // != 0).  A DEVICE column that is only borrowed keeps pointing at the caller's bytes, from `first` on; its offsets are re-based
+    // into a buffer of the library's on the ctx stream.
+    if (first > 0 && first <= last && !copy) {
+      d.data_bytes = last - first;
+      d.own_offsets = ctx->alloc(4 * (size_t)(c.length + 1));
+      copy_in(ctx, d.own_offsets->p, c.offsets, 4 * (size_t)(c.length + 1), c.mem);
+      shift_offsets_kernel<<<dim3((unsigned)ceil_div(c.length + 1, 256)), dim3(256), 0, ctx->stream>>>(d.own_offsets->as<int32_t>(),
+                                                                                                      c.length, first);
+      SQ_HIP(hipGetLastError());
+      d.offsets = d.own_offsets->as<int32_t>();
+      d.values = (const uint8_t *)c.values + first;
+    } else if (first > 0 && first <= last) {
       d.data_bytes = last - first;
       d.own_offsets = ctx->alloc(4 * (size_t)(c.length + 1));
       copy_in(ctx, d.own_offsets->p, c.offsets, 4 * (size_t)(c.length + 1), c.mem);

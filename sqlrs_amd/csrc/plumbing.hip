@@ -764,6 +764,39 @@ int sqlrs_simple_agg_finish(sqlrs_simple_agg_t *a, int out_mem, sqlrs_batch_t **
 }
 void sqlrs_simple_agg_destroy(sqlrs_simple_agg_t *a) { delete a; }
 
+} // extern "C"
+// Rust's Display of a finite f64: the shortest digits that round-trip, written positionally and padded with zeros (1e23 is
+// "100000000000000000000000", not the exact expansion 99999999999999991611392 that to_chars' fixed form gives).
+static void append_f64_display(std::string &s, double v) {
+  char buf[40];
+  auto r = std::to_chars(buf, buf + sizeof(buf), v, std::chars_format::scientific); // [-]d[.ddd]e[+-]xx, shortest
+  *r.ptr = 0; // (at most 24 characters: the exponent is read with atoi)
+  const char *p = buf, *end = r.ptr;
+  if (*p == '-') s.push_back(*p++);
+  const char *e = p;
+  while (e < end && *e != 'e') e++;
+  std::string digits;
+  for (const char *q = p; q < e; q++)
+    if (*q != '.') digits.push_back(*q);
+  int exp10 = 0;
+  if (e < end) exp10 = std::atoi(e + 1);
+  while (digits.size() > 1 && digits.back() == '0') digits.pop_back();
+  const int k = (int)digits.size();
+  if (digits == "0") s.push_back('0');
+  else if (exp10 >= k - 1) {
+    s += digits;
+    s.append((size_t)(exp10 - (k - 1)), '0');
+  } else if (exp10 >= 0) {
+    s.append(digits, 0, (size_t)exp10 + 1);
+    s.push_back('.');
+    s.append(digits, (size_t)exp10 + 1, std::string::npos);
+  } else {
+    s += "0.";
+    s.append((size_t)(-exp10 - 1), '0');
+    s += digits;
+  }
+}
+extern "C" {
 // ------------------------------------------------------------- record_batch_to_string --
 // [ref: src/util/mod.rs:53-80]
 int sqlrs_batch_to_string(sqlrs_ctx_t *ctx, const sqlrs_batch_t *in, char **out) {
@@ -801,11 +834,7 @@ int sqlrs_batch_to_string(sqlrs_ctx_t *ctx, const sqlrs_batch_t *in, char **out)
           const double v = ((const double *)col.values)[row];
           if (std::isnan(v)) s += "NaN";
           else if (std::isinf(v)) s += v < 0 ? "-inf" : "inf";
-          else {
-            char buf[400];
-            auto r = std::to_chars(buf, buf + sizeof(buf), v, std::chars_format::fixed);
-            s.append(buf, r.ptr);
-          }
+          else append_f64_display(s, v);
           break;
         }
         case SQLRS_INT32: s += std::to_string(((const int32_t *)col.values)[row]); break;
