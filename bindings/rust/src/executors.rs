@@ -483,12 +483,27 @@ impl HipLimitExecutor {
         }
     }
 }
-pub struct HipSimpleAggExecutor { pub ctx: Arc<HipCtx>, pub agg_funcs: Vec<BoundExpr>, pub child: BoxedExecutor }
+pub struct HipSimpleAggExecutor {
+    pub ctx: Arc<HipCtx>,
+    pub agg_funcs: Vec<BoundExpr>,
+    pub child: BoxedExecutor, // the Filter's child when `child_filter` is set
+    /// SQLRS_SIMPLE_AGG_REDUCE in `reserved` of the first entry of the create call (opt-in): every batch reduced by one
+    /// streaming kernel instead of a HashAgg over one constant key
+    pub reduce: bool,
+    /// FilterExecutor{expr, child} directly below the operator (filter.rs:7-25): handed to the library as a last entry of the
+    /// create call that carries SQLRS_SIMPLE_AGG_FILTER; evaluated inside the reducing kernel or handed to the inner operator
+    pub child_filter: Option<BoundExpr>,
+}
 impl HipSimpleAggExecutor {
     #[try_stream(boxed, ok = RecordBatch, error = ExecutorError)]
     pub async fn execute(self) {
         let aggs = agg_funcs_of(&self.agg_funcs);
-        let (_l, af) = lower_aggs(&aggs)?;
+        let (_l, mut af) = lower_aggs(&aggs)?;
+        let _fl = match &self.child_filter { Some(p) => Some(lower(p)?), None => None };
+        if let Some(low) = &_fl { // the WHERE below: one more entry, not an aggregate (the library copies the expression)
+            af.push(sqlrs_agg_func_t { func: 0, distinct: 0, return_dtype: 0, reserved: SQLRS_SIMPLE_AGG_FILTER, arg: low.abi() });
+        }
+        if self.reduce { if let Some(first) = af.first_mut() { first.reserved |= SQLRS_SIMPLE_AGG_REDUCE; } }
         let mut a = std::ptr::null_mut();
         self.ctx.check(unsafe { sqlrs_simple_agg_create(self.ctx.raw(), af.len() as i32, af.as_ptr(), &mut a) })?;
         let _g = Guard(a, sqlrs_simple_agg_destroy);
@@ -650,6 +665,16 @@ impl ExecutorBuilder {
         Some(HipLimitExecutor { ctx: self.hip.clone(), limit, offset, child }.execute())
     }
     pub fn hip_visit_physical_simple_agg(&mut self, plan: &PhysicalSimpleAgg) -> Option<BoxedExecutor> {
-        Some(HipSimpleAggExecutor { ctx: self.hip.clone(), agg_funcs: plan.logical().agg_funcs(), child: self.visit(plan.children().first().unwrap().clone()).unwrap() }.execute())
+        self.hip_visit_physical_simple_agg_with(plan, false)
+    }
+    /// `simple_agg_reduce`: the opt-in SQLRS_SIMPLE_AGG_REDUCE for the operator this builds
+    pub fn hip_visit_physical_simple_agg_with(&mut self, plan: &PhysicalSimpleAgg, simple_agg_reduce: bool) -> Option<BoxedExecutor> {
+        let child: PlanRef = plan.children().first().unwrap().clone();
+        // peephole: PhysicalSimpleAgg(PhysicalFilter(x)) hands the predicate to the operator (filter.rs:13-25)
+        let (child, child_filter) = match child.as_physical_filter() {
+            Some(f) => (self.visit(f.children().first().unwrap().clone()).unwrap(), Some(f.logical().expr())),
+            None => (self.visit(child).unwrap(), None),
+        };
+        Some(HipSimpleAggExecutor { ctx: self.hip.clone(), agg_funcs: plan.logical().agg_funcs(), child, reduce: simple_agg_reduce, child_filter }.execute())
     }
 }

@@ -823,19 +823,33 @@ struct SimpleAggExecutor { // simple_agg.rs:9-12: aggregates without GROUP BY, e
   std::vector<BoundAggFunc> agg_funcs;
   BoxedExecutor child;
   std::vector<std::string> output_names;
+  bool reduce = false; // SQLRS_SIMPLE_AGG_REDUCE on the first entry of the create call: every batch reduced by one streaming kernel instead of a HashAgg over one constant key
+  // FilterExecutor{expr = child_filter, child} directly below the operator (filter.rs:7-25), handed to the library as a last
+  // entry of the create call that carries SQLRS_SIMPLE_AGG_FILTER: same result as wrapping `child` in a FilterExecutor
+  std::optional<BoundExpr> child_filter;
+  int64_t *reduced_batches = nullptr; // out (optional): pushes the reduce route consumed (the count `simple_reduce_batches` of sqlrs_ctx_profile_read)
+  static int64_t reduce_witness(sqlrs_ctx_t *c) {
+    const char *names[1024]; double ms[1024]; int64_t count[1024];
+    const int n = sqlrs_ctx_profile_read(c, 1024, names, ms, count);
+    for (int i = 0; i < n && i < 1024; i++) if (std::string(names[i]) == "simple_reduce_batches") return count[i];
+    return 0;
+  }
   BoxedExecutor execute() {
     struct S : Executor {
       HipCtxRef ctx; BoxedExecutor child; sqlrs_simple_agg_t *a = nullptr; bool done = false; std::vector<std::string> names;
+      int64_t *reduced = nullptr;
       ~S() override { if (a) sqlrs_simple_agg_destroy(a); }
       std::optional<RecordBatch> next() override {
         if (done) return std::nullopt;
         done = true;
+        const int64_t before = reduced ? reduce_witness(ctx->raw) : 0;
         while (auto b = child->next()) { // simple_agg.rs:35-57
           detail::AbiBatch in(*b);
           ctx->check(sqlrs_simple_agg_push(a, &in.b));
         }
         sqlrs_batch_t *out = nullptr;
         ctx->check(sqlrs_simple_agg_finish(a, SQLRS_MEM_HOST, &out));
+        if (reduced) *reduced = reduce_witness(ctx->raw) - before;
         RecordBatch rb = detail::import_batch(out, nullptr);
         auto sch = std::make_shared<Schema>(*rb.schema);
         for (size_t i = 0; i < sch->size() && i < names.size(); i++) (*sch)[i].name = names[i];
@@ -850,7 +864,14 @@ struct SimpleAggExecutor { // simple_agg.rs:9-12: aggregates without GROUP BY, e
     for (auto &f : agg_funcs) al.push_back(detail::lower(f.exprs.at(0))); // only exprs[0] is read (simple_agg.rs:38-41)
     for (size_t i = 0; i < agg_funcs.size(); i++)
       af.push_back(sqlrs_agg_func_t{(int32_t)agg_funcs[i].func, agg_funcs[i].distinct, (int32_t)agg_funcs[i].return_type, 0, al[i].abi()});
+    std::optional<detail::Lowered> fl;
+    if (child_filter) { // the WHERE below: one more entry, not an aggregate (the library copies the expression)
+      fl = detail::lower(*child_filter);
+      af.push_back(sqlrs_agg_func_t{0, 0, 0, SQLRS_SIMPLE_AGG_FILTER, fl->abi()});
+    }
+    if (reduce && !af.empty()) af[0].reserved |= SQLRS_SIMPLE_AGG_REDUCE;
     ctx->check(sqlrs_simple_agg_create(ctx->raw, (int)af.size(), af.data(), &s->a));
+    s->reduced = reduced_batches;
     return s;
   }
 };
@@ -976,14 +997,18 @@ struct PlanNode {
 };
 
 // ExecutorBuilder (src/executor/mod.rs:36-56, PlanVisitor impl :87-200): one visit_physical_* per node, each
-// instantiating the operator struct exactly as the reference does — plus TWO peepholes in visit_physical_hash_agg
-// and one in visit_physical_limit (PhysicalLimit(PhysicalOrder(child)) -> OrderExecutor{.., limit_hint = offset + limit}):
+// instantiating the operator struct exactly as the reference does — plus TWO peepholes in visit_physical_hash_agg, one in
+// visit_physical_simple_agg and one in visit_physical_limit (PhysicalLimit(PhysicalOrder(child)) -> OrderExecutor{..,
+// limit_hint = offset + limit}):
 //
 //   PhysicalHashAgg(PhysicalHashJoin[Inner, no join filter](l, PhysicalFilter?(r)))
 //        -> HashJoinAggExecutor{.., probe_filter = the Filter's expr}     (sqlrs_join_agg_* + set_probe_filter)
 //
 //   PhysicalHashAgg(PhysicalFilter(child))
 //        -> HashAggExecutor{.., child_filter = the Filter's expr}         (sqlrs_hash_agg_set_filter)
+//
+//   PhysicalSimpleAgg(PhysicalFilter(child))
+//        -> SimpleAggExecutor{.., child_filter = the Filter's expr}       (SQLRS_SIMPLE_AGG_FILTER)
 //
 // which is how the bench's headline plan is reached from a reference-shaped plan tree.  The library decides at
 // run time whether its fused route applies (unique build keys, group key = join key, probe-side arguments; a
@@ -993,7 +1018,8 @@ struct ExecutorBuilder {
   HipCtxRef ctx;
   bool fuse_join_agg = true; // false = one executor per node, as the reference builds them
   bool order_limit_all_keys = false; // opt-in: the ORDER BY ... LIMIT peephole also serves Utf8 / nullable / expression first keys
-  int64_t last_fused_batches = 0, last_filter_fused_batches = 0;
+  bool simple_agg_reduce = false;    // opt-in: SimpleAggExecutor{.., reduce = true} (SQLRS_SIMPLE_AGG_REDUCE)
+  int64_t last_fused_batches = 0, last_filter_fused_batches = 0, last_reduced_batches = 0;
   int rewrites = 0;
 
   BoxedExecutor build(const PlanRef &plan) { return visit(plan); } // mod.rs:45-47
@@ -1032,9 +1058,19 @@ struct ExecutorBuilder {
     ex.ctx = ctx; ex.expr = plan.expr; ex.child = visit(plan.children().front());
     return ex.execute();
   }
-  BoxedExecutor visit_physical_simple_agg(const PlanNode &plan) { // mod.rs:151-161
+  BoxedExecutor visit_physical_simple_agg(const PlanNode &plan) { // mod.rs:151-161 + the peephole
     SimpleAggExecutor ex;
-    ex.ctx = ctx; ex.agg_funcs = plan.agg_funcs; ex.child = visit(plan.children().front()); ex.output_names = plan.output_names;
+    ex.ctx = ctx; ex.agg_funcs = plan.agg_funcs; ex.output_names = plan.output_names;
+    ex.reduce = simple_agg_reduce;
+    ex.reduced_batches = &last_reduced_batches;
+    const PlanRef &child = plan.children().front();
+    if (fuse_join_agg && child->kind == PlanNode::PhysicalFilter) { // FilterExecutor directly below: handed to the operator
+      ex.child_filter = child->expr;
+      ex.child = visit(child->children().front());
+      rewrites++;
+    } else {
+      ex.child = visit(child);
+    }
     return ex.execute();
   }
   BoxedExecutor visit_physical_hash_agg(const PlanNode &plan) { // mod.rs:163-174 + the peephole

@@ -176,7 +176,7 @@ typedef struct sqlrs_agg_func {
   int32_t func;         /* sqlrs_agg_kind_t */
   int32_t distinct;     /* BoundAggFunc.distinct */
   int32_t return_dtype; /* BoundAggFunc.return_type (SUM accumulates in this type, sum.rs:54) */
-  int32_t reserved;
+  int32_t reserved;     /* 0, or in sqlrs_simple_agg_create: SQLRS_SIMPLE_AGG_REDUCE (first entry) / SQLRS_SIMPLE_AGG_FILTER (last entry) */
   sqlrs_expr_t arg;     /* BoundAggFunc.exprs[0]  (only exprs[0] is read: hash_agg.rs:65) */
 } sqlrs_agg_func_t;
 
@@ -690,6 +690,42 @@ int sqlrs_simple_agg_create(sqlrs_ctx_t *ctx, int num_aggs, const sqlrs_agg_func
 int sqlrs_simple_agg_push(sqlrs_simple_agg_t *a, const sqlrs_batch_t *in);
 int sqlrs_simple_agg_finish(sqlrs_simple_agg_t *a, int out_mem, sqlrs_batch_t **out);
 void sqlrs_simple_agg_destroy(sqlrs_simple_agg_t *a);
+/* Two opt-in flags of sqlrs_simple_agg_create, in `reserved` of its sqlrs_agg_func_t entries (0, the default, leaves the operator
+ * as it is; flags of the create call, not entry points of their own: the set of functions is unchanged).
+ *
+ * SQLRS_SIMPLE_AGG_REDUCE in `reserved` of the FIRST entry: the reduce route [ref: simple_agg.rs:27-65, one accumulator per
+ * aggregate updated batch by batch].  Without it the operator is a HashAgg over one constant key: it keeps copies of the
+ * pushed key and argument columns until finish and resolves every row through the group table.  With it every pushed batch
+ * is consumed by one grid-stride kernel that reads each referenced column once, evaluates the filter (below) and the argument
+ * expressions row by row in registers and reduces into one partial record per workgroup, and a second launch that folds
+ * those records, in a fixed tree, into a few persistent cells; the operator keeps nothing of the batch (DEVICE columns
+ * are read stream-ordered, as the borrowing rules say).  Results are those of the default route; SUM over Float64 within the
+ * summation-order tolerance, and bit for bit the same for the same sequence of batches on one device (no floating-point
+ * atomics).  Small fixed-width HOST batches are staged as for sqlrs_hash_agg_push (the referenced columns only) and reduced
+ * together per 2^22 rows or at finish.
+ * Admitted — decided once, from the column types of the FIRST pushed batch, for the operator's whole life: every aggregate is
+ * a non-DISTINCT COUNT / SUM / MIN / MAX whose argument (cast to the return type for SUM) is an expression over Int32 /
+ * Int64 / Float64 columns and constants with casts and + - * / (<= 24 nodes, stack <= 8) and an Int32 / Int64 / Float64
+ * result; the filter, if any, is such an expression with comparisons and AND / OR and a Boolean result; at most 4 distinct
+ * (argument, cast) pairs — any number of aggregates over them — and between 1 and 16 referenced columns.  Anything else (a
+ * Utf8 / Boolean operand, DISTINCT, MIN / MAX over Utf8, a fifth argument, a longer expression) falls back: the operator
+ * behaves exactly as without the flag.  A later batch whose referenced columns differ in type from the first batch's is
+ * refused at its push with the status the inner operator has for batches of different schemas (SQLRS_ERR_ARROW).
+ * Errors: a division by zero on a kept row with valid operands is recorded on the device and reported by
+ * sqlrs_simple_agg_finish (SQLRS_ERR_ARROW, the evaluator's text), not by the push that met it.
+ * Witness: the count `simple_reduce_batches` of sqlrs_ctx_profile_read — pushes the reduce route consumed on this ctx, empty
+ * batches included, counted at the push; an operator that is not admitted does not move it.
+ *
+ * SQLRS_SIMPLE_AGG_FILTER in `reserved` of the LAST entry (num_aggs >= 2): that entry is not an aggregate — its `arg` is the
+ * predicate of a FilterExecutor sitting directly below the operator, PhysicalSimpleAgg(PhysicalFilter(child)), the shape of
+ * `SELECT sum(x) FROM t WHERE ...` [ref: filter.rs:13-25 feeding simple_agg.rs:27-65]; its other fields are not read and the
+ * output has num_aggs - 1 columns.  Results are identical to sqlrs_filter_push on every batch followed by
+ * sqlrs_simple_agg_push of its output: rows whose mask is false or NULL are dropped; when every row is dropped but a batch
+ * was pushed the result is COUNT = 0 and NULL for the others; no batch pushed is the error it is without the flag.  With the
+ * reduce route the predicate is evaluated inside the reducing kernel (the filtered columns are never written); otherwise it
+ * is handed to the inner operator (sqlrs_hash_agg_set_filter).  An empty `arg` means no filter. */
+#define SQLRS_SIMPLE_AGG_REDUCE 1
+#define SQLRS_SIMPLE_AGG_FILTER 2
 
 /* [ref: src/util/mod.rs:53-80  record_batch_to_string]  The sqllogictest text form of a batch (host or
  * device resident): one line per row, one blank between columns, NULL -> "NULL", empty string ->

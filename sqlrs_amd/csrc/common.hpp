@@ -229,6 +229,7 @@ struct Ctx {
   // SQLRS_EXPR_STAGE_ALL_TYPES (host_stage.hpp), reported like the route counts behind the ORDER BY entries:
   int64_t stage_all_types_batches = 0; // HOST batches a stage carrying the flag took (profile: "stage_all_types_batches")
   int64_t stage_stitch_flushes = 0;    // flushes of such a stage that ran the stitch kernels (profile: "stage_stitch_flushes")
+  int64_t simple_reduce_batches = 0;   // pushes the reduce route of SimpleAgg consumed (simple_reduce.hip; profile: "simple_reduce_batches")
   std::shared_ptr<void> small_ring; // the pinned ring of the single-batch async path (small_async.hpp), created on first use
   void sync() { SQ_HIP(hipStreamSynchronize(stream)); }
   // copies `bytes` from device to the pinned area and synchronises; returns host pointer

@@ -1533,6 +1533,16 @@ int sqlrs_ctx_profile_read(sqlrs_ctx_t *ctx, int cap, const char **names, double
     }
     n++;
   }
+  // (count: pushes the reduce route of SimpleAgg consumed, simple_reduce.hip — no agg_ prefix: the aggregate routes above are at
+  //  rest while it runs; behind every older entry)
+  if (ctx->simple_reduce_batches) {
+    if (n < cap) {
+      names[n] = "simple_reduce_batches";
+      total_ms[n] = 0;
+      launches[n] = ctx->simple_reduce_batches;
+    }
+    n++;
+  }
   return n;
 }
 

@@ -15,6 +15,7 @@
 #include "host_stage.hpp"
 #include "device_utils.hpp"
 #include "prims.hpp"
+#include "simple_agg_state.hpp"
 #include "small_async.hpp"
 
 using namespace sq;
@@ -23,6 +24,7 @@ extern "C" {
 int sqlrs_hash_agg_create(sqlrs_ctx_t *, int, const sqlrs_expr_t *, int, const sqlrs_agg_func_t *, sqlrs_hash_agg_t **);
 int sqlrs_hash_agg_push(sqlrs_hash_agg_t *, const sqlrs_batch_t *);
 int sqlrs_hash_agg_finish(sqlrs_hash_agg_t *, int, sqlrs_batch_t **);
+int sqlrs_hash_agg_set_filter(sqlrs_hash_agg_t *, const sqlrs_expr_t *);
 void sqlrs_hash_agg_destroy(sqlrs_hash_agg_t *);
 void sqlrs_batch_release(sqlrs_batch_t *);
 }
@@ -77,15 +79,7 @@ struct sqlrs_limit {
 };
 
 // ======================================================================= SimpleAgg ==
-struct sqlrs_simple_agg {
-  Ctx *ctx = nullptr;
-  sqlrs_hash_agg_t *inner = nullptr; // HashAgg over one constant key: same accumulators, one group
-  std::vector<int32_t> funcs, return_dtypes;
-  bool saw_batch = false;
-  ~sqlrs_simple_agg() {
-    if (inner) sqlrs_hash_agg_destroy(inner);
-  }
-};
+// (struct sqlrs_simple_agg: simple_agg_state.hpp, shared with its reduce route in simple_reduce.hip)
 
 // ============================================================================= CSV ==
 namespace {
@@ -712,6 +706,13 @@ int sqlrs_simple_agg_create(sqlrs_ctx_t *ctx, int num_aggs, const sqlrs_agg_func
   return guard(ctx, [&] {
     auto a = std::unique_ptr<sqlrs_simple_agg>(new sqlrs_simple_agg());
     a->ctx = ctx;
+    // the two flags of the create call (sqlrs_hip.h): the reduce route on the first entry, a last entry that is the WHERE below
+    a->reduce = num_aggs > 0 && aggs && (aggs[0].reserved & SQLRS_SIMPLE_AGG_REDUCE) != 0;
+    if (num_aggs > 0 && aggs && (aggs[num_aggs - 1].reserved & SQLRS_SIMPLE_AGG_FILTER) != 0) {
+      if (num_aggs < 2) fail(SQLRS_ERR_INTERNAL, "a filter entry needs an aggregate in front of it");
+      num_aggs--;
+      a->filter = aggs[num_aggs].arg.num_nodes > 0 ? expr_from_abi(&aggs[num_aggs].arg) : Expr();
+    }
     sqlrs_expr_node_t key;
     std::memset(&key, 0, sizeof(key));
     key.op = SQLRS_EXPR_CONSTANT;
@@ -722,18 +723,37 @@ int sqlrs_simple_agg_create(sqlrs_ctx_t *ctx, int num_aggs, const sqlrs_agg_func
     for (int i = 0; i < num_aggs; i++) {
       a->funcs.push_back(aggs[i].func);
       a->return_dtypes.push_back(aggs[i].return_dtype);
+      a->distinct.push_back(aggs[i].distinct);
+      a->args.push_back(expr_from_abi(&aggs[i].arg));
     }
     *out = a.release();
   });
 }
+// The route is decided by the first push.  The filter is kept here until then: the reduce route evaluates it in its kernel, every
+// other operator hands it to the inner HashAgg (sqlrs_hash_agg_set_filter) in front of the first batch.
 int sqlrs_simple_agg_push(sqlrs_simple_agg_t *a, const sqlrs_batch_t *in) {
   a->saw_batch = true;
+  if (!a->decided) {
+    bool taken = false;
+    int st = guard(a->ctx, [&] { taken = sr_decide(a, in); });
+    if (st != SQLRS_OK) return st;
+    if (!taken && !a->filter.empty()) { // [ref: filter.rs:13-25 feeding simple_agg.rs:35]
+      std::vector<sqlrs_expr_node_t> nodes = a->filter.nodes;
+      for (size_t i = 0; i < nodes.size(); i++) nodes[i].s = a->filter.strings[i].empty() ? nullptr : a->filter.strings[i].c_str();
+      sqlrs_expr_t fe{nodes.data(), (int32_t)nodes.size(), 0};
+      st = sqlrs_hash_agg_set_filter(a->inner, &fe);
+      if (st != SQLRS_OK) return st;
+    }
+    a->decided = true; // (only now: a push that failed above decides again, it never leaves the filter behind)
+  }
+  if (a->sr) return guard(a->ctx, [&] { sr_push(a, in); });
   return sqlrs_hash_agg_push(a->inner, in);
 }
 // [ref: simple_agg.rs:58-64] exactly one row; no input rows at all: COUNT = 0, everything else NULL
 int sqlrs_simple_agg_finish(sqlrs_simple_agg_t *a, int out_mem, sqlrs_batch_t **out) {
   sqlrs_batch_t *g = nullptr;
   if (!a->saw_batch) return guard(a->ctx, [&] { fail(SQLRS_ERR_INTERNAL, "simple agg finished without any input batch"); });
+  if (a->sr) return guard(a->ctx, [&] { sr_finish(a, out_mem, out); });
   int st = sqlrs_hash_agg_finish(a->inner, SQLRS_MEM_DEVICE, &g);
   if (st != SQLRS_OK) return st;
   st = guard(a->ctx, [&] {

@@ -570,21 +570,44 @@ class SimpleAggExecutor:
     """``SimpleAggExecutor { agg_funcs, child }`` (simple_agg.rs:10-13)."""
 
     def __init__(self, backend: abi.Backend, agg_funcs: List[AggFunc], child: Iterable, out_mem: int = abi.MEM_HOST,
-                 output_names: Optional[Sequence[str]] = None):
+                 output_names: Optional[Sequence[str]] = None, reduce: bool = False, child_filter: Optional[BoundExpr] = None):
         self.backend, self.agg_funcs, self.child, self.out_mem, self.output_names = backend, agg_funcs, child, out_mem, output_names
+        # SQLRS_SIMPLE_AGG_REDUCE on the first entry of the create call: every batch reduced by one streaming kernel instead of a
+        # HashAgg over one constant key (opt-in; a backend that has no such route — the oracle — ignores the field)
+        self.reduce = reduce
+        # FilterExecutor{expr = child_filter, child} directly below the operator (filter.rs:7-25), handed to the library as a last
+        # entry of the create call that carries SQLRS_SIMPLE_AGG_FILTER; a backend that is not the HIP library gets the
+        # FilterExecutor itself: same result
+        self.child_filter = child_filter
+        self.reduced_batches = 0  # after execute(): pushes the reduce route consumed (the count `simple_reduce_batches`)
 
     def execute(self):
         be = self.backend
         keep = []
-        aggs = (abi.AggFunc * max(len(self.agg_funcs), 1))(*[a.abi_struct(keep) for a in self.agg_funcs])
+        is_hip = be.version().startswith("sqlrs-hip")
+        funcs = [a.abi_struct(keep) for a in self.agg_funcs]
+        child = self.child
+        if self.child_filter is not None:
+            if is_hip:
+                pf = self.child_filter.pack()
+                keep.append(pf)
+                funcs.append(abi.AggFunc(0, 0, 0, abi.SIMPLE_AGG_FILTER, pf.abi))
+            else:
+                child = FilterExecutor(be, self.child_filter, child).execute()
+        if self.reduce and funcs and is_hip:
+            funcs[0].reserved |= abi.SIMPLE_AGG_REDUCE
+        aggs = (abi.AggFunc * max(len(funcs), 1))(*funcs)
+        witness = (lambda: be.profile_read().get("simple_reduce_batches", (0, 0))[1]) if is_hip else (lambda: 0)
+        before = witness()
         h = C.c_void_p()
-        be.check(be.fn("simple_agg_create")(be.ctx, len(self.agg_funcs), aggs, C.byref(h)))
+        be.check(be.fn("simple_agg_create")(be.ctx, len(funcs), aggs, C.byref(h)))
         try:
-            for batch in self.child:  # simple_agg.rs:35-56
+            for batch in child:  # simple_agg.rs:35-56
                 b = abi.as_batch(batch)
                 be.check(be.fn("simple_agg_push")(h, b.ptr))
             out = C.POINTER(abi.Batch)()
             be.check(be.fn("simple_agg_finish")(h, self.out_mem, C.byref(out)))
+            self.reduced_batches = witness() - before
             yield _emit(be, out, self.out_mem, self.output_names)
         finally:
             be.fn("simple_agg_destroy")(h)
