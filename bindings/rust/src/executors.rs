@@ -61,7 +61,9 @@ fn agg_schema(group_by: &[BoundExpr], aggs: &[BoundAggFunc], input: &RecordBatch
 }
 
 // ------------------------------------------------------------------ Filter --
-pub struct HipFilterExecutor { pub ctx: Arc<HipCtx>, pub expr: BoundExpr, pub child: BoxedExecutor }
+/// `fused_eval` (SQLRS_EXPR_FUSED_EVAL in `reserved` of the predicate, opt-in): a predicate off the two one-pass routes is
+/// evaluated by one program kernel per batch instead of node by node; the same batches either way.
+pub struct HipFilterExecutor { pub ctx: Arc<HipCtx>, pub expr: BoundExpr, pub child: BoxedExecutor, pub fused_eval: bool }
 /// The same operator pulling `group` batches of its child at a time and handing them to `sqlrs_filter_push_many`: the same
 /// stream of output batches (one per input batch, filter.rs:15-24) at one upload / launch sequence / download per GROUP —
 /// 1024-row CSV batches (storage/csv.rs:105): 23 -> 934 Mrows/s from a native caller.
@@ -139,7 +141,9 @@ impl HipFilterExecutor {
     pub async fn execute(self) {
         let expr = lower(&self.expr)?;
         let mut f = std::ptr::null_mut();
-        self.ctx.check(unsafe { sqlrs_filter_create(self.ctx.raw(), &expr.abi(), &mut f) })?;
+        let mut e = expr.abi();
+        if self.fused_eval { e.reserved = SQLRS_EXPR_FUSED_EVAL; }
+        self.ctx.check(unsafe { sqlrs_filter_create(self.ctx.raw(), &e, &mut f) })?;
         let _g = Guard(f, sqlrs_filter_destroy);
         #[for_await]
         for batch in self.child { // filter.rs:15-24: one output batch per input batch, empty ones included
@@ -296,7 +300,9 @@ impl HipOrderExecutor {
 }
 
 // -------------------------------------------- Project / Limit / SimpleAgg --
-pub struct HipProjectExecutor { pub ctx: Arc<HipCtx>, pub exprs: Vec<BoundExpr>, pub child: BoxedExecutor }
+/// `fused_eval` (SQLRS_EXPR_FUSED_EVAL in `reserved` of the first expression, opt-in): the computed columns are evaluated by
+/// program kernels, up to four per launch, instead of node by node; the same batches either way.
+pub struct HipProjectExecutor { pub ctx: Arc<HipCtx>, pub exprs: Vec<BoundExpr>, pub child: BoxedExecutor, pub fused_eval: bool }
 /// The same operator pulling `group` batches of its child at a time and handing them to `sqlrs_project_push_many`: the same
 /// stream of output batches (one per input batch, project.rs:15-27) at one upload / launch sequence / download per GROUP.
 pub struct HipProjectManyExecutor { pub ctx: Arc<HipCtx>, pub exprs: Vec<BoundExpr>, pub child: BoxedExecutor, pub group: usize }
@@ -373,7 +379,8 @@ impl HipProjectAsyncExecutor {
 impl HipProjectExecutor {
     #[try_stream(boxed, ok = RecordBatch, error = ExecutorError)]
     pub async fn execute(self) {
-        let (_l, ex) = lower_all(&self.exprs)?;
+        let (_l, mut ex) = lower_all(&self.exprs)?;
+        if self.fused_eval { if let Some(first) = ex.first_mut() { first.reserved = SQLRS_EXPR_FUSED_EVAL; } }
         let mut p = std::ptr::null_mut();
         self.ctx.check(unsafe { sqlrs_project_create(self.ctx.raw(), ex.len() as i32, ex.as_ptr(), &mut p) })?;
         let _g = Guard(p, sqlrs_project_destroy);
@@ -593,7 +600,7 @@ impl HipHashJoinAggExecutor {
 /// ones at mod.rs:103-114, 127-137, 139-149, 151-161, 163-174, 176-187, 189-199.
 impl ExecutorBuilder {
     pub fn hip_visit_physical_filter(&mut self, plan: &PhysicalFilter) -> Option<BoxedExecutor> {
-        Some(HipFilterExecutor { ctx: self.hip.clone(), expr: plan.logical().expr(), child: self.visit(plan.children().first().unwrap().clone()).unwrap() }.execute())
+        Some(HipFilterExecutor { ctx: self.hip.clone(), expr: plan.logical().expr(), child: self.visit(plan.children().first().unwrap().clone()).unwrap(), fused_eval: false }.execute())
     }
     pub fn hip_visit_physical_hash_join(&mut self, plan: &PhysicalHashJoin) -> Option<BoxedExecutor> {
         Some(HipHashJoinExecutor {
@@ -640,7 +647,7 @@ impl ExecutorBuilder {
         Some(HipOrderExecutor { ctx: self.hip.clone(), order_by: plan.logical().order_by(), child: self.visit(plan.children().first().unwrap().clone()).unwrap(), limit_hint: 0, limit_all_keys: false, stage_all_types: false }.execute())
     }
     pub fn hip_visit_physical_project(&mut self, plan: &PhysicalProject) -> Option<BoxedExecutor> {
-        Some(HipProjectExecutor { ctx: self.hip.clone(), exprs: plan.logical().exprs(), child: self.visit(plan.children().first().unwrap().clone()).unwrap() }.execute())
+        Some(HipProjectExecutor { ctx: self.hip.clone(), exprs: plan.logical().exprs(), child: self.visit(plan.children().first().unwrap().clone()).unwrap(), fused_eval: false }.execute())
     }
     pub fn hip_visit_physical_cross_join(&mut self, plan: &PhysicalCrossJoin) -> Option<BoxedExecutor> { // executor/mod.rs:116-125
         Some(HipCrossJoinExecutor { ctx: self.hip.clone(), left_child: self.visit(plan.left()).unwrap(), right_child: self.visit(plan.right()).unwrap(),

@@ -393,6 +393,7 @@ struct FilterExecutor { // filter.rs:7-10
   // caller never waits for the device: 22 -> 168 Mrows/s at 1024-row batches, without regrouping the child's stream
   size_t depth = 0;
   bool async_all_types = false; // sqlrs_filter_set_async_all_types: with depth > 0, predicates over Utf8 / Boolean columns and batches with Boolean columns in one launch too
+  bool fused_eval = false;      // SQLRS_EXPR_FUSED_EVAL on the predicate: sqlrs_filter_push evaluates a predicate off the two one-pass routes by one program kernel
   BoxedExecutor execute() {
     struct S : Executor {
       HipCtxRef ctx; BoxedExecutor child; sqlrs_filter_t *f = nullptr; detail::Lowered low;
@@ -452,6 +453,7 @@ struct FilterExecutor { // filter.rs:7-10
     auto s = std::make_unique<S>();
     s->ctx = ctx; s->child = std::move(child); s->low = detail::lower(expr); s->group = group; s->depth = depth;
     sqlrs_expr_t e = s->low.abi();
+    if (fused_eval) e.reserved = SQLRS_EXPR_FUSED_EVAL;
     ctx->check(sqlrs_filter_create(ctx->raw, &e, &s->f));
     if (async_all_types) ctx->check(sqlrs_filter_set_async_all_types(s->f, 1));
     return s;
@@ -713,6 +715,7 @@ struct ProjectExecutor { // project.rs:6-9
   size_t group = 0;                      // child batches per library call (see FilterExecutor)
   size_t depth = 0;                      // sqlrs_project_push_async, that many tickets in flight (see FilterExecutor)
   bool async_all_types = false;          // sqlrs_project_set_async_all_types: computed columns over Utf8 / Boolean columns in one launch too
+  bool fused_eval = false;               // SQLRS_EXPR_FUSED_EVAL on the first expression: sqlrs_project_push evaluates the computed columns by program kernels
   BoxedExecutor execute() {
     struct S : Executor {
       HipCtxRef ctx; BoxedExecutor child; sqlrs_project_t *p = nullptr; std::vector<std::string> names;
@@ -782,6 +785,7 @@ struct ProjectExecutor { // project.rs:6-9
     std::vector<sqlrs_expr_t> ex;
     for (auto &e : exprs) low.push_back(detail::lower(e));
     for (auto &l : low) ex.push_back(l.abi());
+    if (fused_eval && !ex.empty()) ex[0].reserved = SQLRS_EXPR_FUSED_EVAL;
     ctx->check(sqlrs_project_create(ctx->raw, (int)ex.size(), ex.data(), &s->p));
     if (async_all_types) ctx->check(sqlrs_project_set_async_all_types(s->p, 1));
     return s;
@@ -1019,6 +1023,7 @@ struct ExecutorBuilder {
   bool fuse_join_agg = true; // false = one executor per node, as the reference builds them
   bool order_limit_all_keys = false; // opt-in: the ORDER BY ... LIMIT peephole also serves Utf8 / nullable / expression first keys
   bool simple_agg_reduce = false;    // opt-in: SimpleAggExecutor{.., reduce = true} (SQLRS_SIMPLE_AGG_REDUCE)
+  bool fused_eval = false;           // opt-in: FilterExecutor / ProjectExecutor{.., fused_eval = true} (SQLRS_EXPR_FUSED_EVAL)
   int64_t last_fused_batches = 0, last_filter_fused_batches = 0, last_reduced_batches = 0;
   int rewrites = 0;
 
@@ -1051,11 +1056,13 @@ struct ExecutorBuilder {
   BoxedExecutor visit_physical_project(const PlanNode &plan) { // mod.rs:127-137
     ProjectExecutor ex;
     ex.ctx = ctx; ex.exprs = plan.exprs; ex.child = visit(plan.children().front()); ex.output_names = plan.output_names;
+    ex.fused_eval = fused_eval;
     return ex.execute();
   }
   BoxedExecutor visit_physical_filter(const PlanNode &plan) { // mod.rs:139-149
     FilterExecutor ex;
     ex.ctx = ctx; ex.expr = plan.expr; ex.child = visit(plan.children().front());
+    ex.fused_eval = fused_eval;
     return ex.execute();
   }
   BoxedExecutor visit_physical_simple_agg(const PlanNode &plan) { // mod.rs:151-161 + the peephole

@@ -152,7 +152,8 @@ typedef struct sqlrs_expr_node {
 typedef struct sqlrs_expr {
   const sqlrs_expr_node_t *nodes; /* postfix order */
   int32_t num_nodes;
-  int32_t reserved; /* 0, or on the first key expression of a blocking operator's create call: SQLRS_EXPR_STAGE_ALL_TYPES (see sqlrs_hash_agg_push) */
+  int32_t reserved; /* 0, or on the first key expression of a blocking operator's create call: SQLRS_EXPR_STAGE_ALL_TYPES (see sqlrs_hash_agg_push);
+                     * on the predicate of sqlrs_filter_create / exprs[0] of sqlrs_project_create: SQLRS_EXPR_FUSED_EVAL (see sqlrs_filter_push) */
 } sqlrs_expr_t;
 
 /* [ref: src/binder/table/join.rs:18-24  enum JoinType] (Cross never reaches HashJoin:
@@ -276,6 +277,30 @@ int sqlrs_batch_export_arrow(sqlrs_ctx_t *ctx, sqlrs_batch_t *batch, const char 
  * is false or NULL dropped, empty batches still returned. */
 typedef struct sqlrs_filter sqlrs_filter_t;
 int sqlrs_filter_create(sqlrs_ctx_t *ctx, const sqlrs_expr_t *expr, sqlrs_filter_t **out);
+/* Opt-in, SQLRS_EXPR_FUSED_EVAL in `reserved` of the predicate handed to sqlrs_filter_create, or of exprs[0] handed to
+ * sqlrs_project_create (0, the default, leaves every decision as it is; a flag of the create calls like
+ * SQLRS_EXPR_STAGE_ALL_TYPES, not a setter: the set of entry points is unchanged): whole expressions are evaluated in one
+ * pass.  Results never depend on it.  It affects only sqlrs_filter_push and sqlrs_project_push — the synchronous single-batch
+ * calls, HOST or DEVICE input, any out_mem.  *_push_many, *_push_async, sqlrs_eval_expr and the inner Filters of HashAgg /
+ * join_agg / the join filter are out of scope and run as without it.
+ *
+ * Filter: the two existing one-pass routes (`column OP constant`; a conjunction of up to four such terms over int64 / float64
+ * columns without NULLs) are tried first, unchanged.  A predicate that then compiles (below) is evaluated row by row by ONE
+ * kernel that writes the selection's mask words; tile offsets and the compaction of the columns follow as for any mask.
+ * Anything else takes the per-node evaluator as without the flag.
+ * Project: a bare column reference and a bare constant keep their handling (a reference shares the input's buffers); every
+ * other expression is a computed column.  If every computed column compiles they are evaluated by the program kernel, up to
+ * four per launch; if even one does not, the whole push takes the per-node evaluator, so the first error raised is the same.
+ * What compiles: int32 / int64 / float64 / boolean columns and constants as operands, an int32 / int64 / float64 / boolean
+ * result, at most 24 expression nodes, 8 operands in flight and 16 distinct referenced columns per launch.  utf8 operands,
+ * operands of two different types, unsupported casts and longer expressions do not: the per-node evaluator runs and raises
+ * whatever there is to raise.  A batch of 0 rows takes the per-node evaluator as well.
+ * Results are those without the flag: row order, validity, and the values bit for bit on every valid row (the value under a
+ * NULL of a computed column is 0; a computed column always carries a validity bitmap, null_count -1).  A valid row that divides by
+ * zero makes the push return SQLRS_ERR_ARROW "Divide by zero error" and no batch; the operator stays usable.
+ * Witnesses (sqlrs_ctx_profile_read): "fused_eval_filter_batches" — pushes whose mask the program kernel wrote —
+ * and "fused_eval_project_columns" — computed columns it wrote; "expr_binary" / "expr_cast" do not move on such a push. */
+#define SQLRS_EXPR_FUSED_EVAL 2
 int sqlrs_filter_push(sqlrs_filter_t *f, const sqlrs_batch_t *in, int out_mem, sqlrs_batch_t **out);
 /* n iterations of the loop in ONE call: out[i] (n entries) is what sqlrs_filter_push(in[i]) returns — one output batch
  * per input batch, in order, empty ones included [ref: filter.rs:15-24] — for the reference's batch shape, 1024-row

@@ -22,6 +22,8 @@ MEM_HOST, MEM_DEVICE = 0, 1
 ORDER_LIMIT_ALL_KEYS = 1  # SQLRS_ORDER_LIMIT_ALL_KEYS: `reserved` of the first OrderBy of order_create
 # SQLRS_EXPR_STAGE_ALL_TYPES: `reserved` of the first key Expr of hash_agg / hash_join / join_agg / order _create
 EXPR_STAGE_ALL_TYPES = 1
+# SQLRS_EXPR_FUSED_EVAL: `reserved` of the predicate of filter_create / of the first Expr of project_create
+EXPR_FUSED_EVAL = 2
 # `reserved` of the entries of simple_agg_create: SQLRS_SIMPLE_AGG_REDUCE on the first one, SQLRS_SIMPLE_AGG_FILTER on a last one
 # that is the WHERE below the operator, not an aggregate
 SIMPLE_AGG_REDUCE, SIMPLE_AGG_FILTER = 1, 2

@@ -230,6 +230,9 @@ struct Ctx {
   int64_t stage_all_types_batches = 0; // HOST batches a stage carrying the flag took (profile: "stage_all_types_batches")
   int64_t stage_stitch_flushes = 0;    // flushes of such a stage that ran the stitch kernels (profile: "stage_stitch_flushes")
   int64_t simple_reduce_batches = 0;   // pushes the reduce route of SimpleAgg consumed (simple_reduce.hip; profile: "simple_reduce_batches")
+  // SQLRS_EXPR_FUSED_EVAL (expr_fused.hip), reported behind it:
+  int64_t fused_eval_filter_batches = 0;  // sqlrs_filter_push calls whose mask the program kernel wrote (profile: "fused_eval_filter_batches")
+  int64_t fused_eval_project_columns = 0; // computed columns of sqlrs_project_push it wrote (profile: "fused_eval_project_columns")
   std::shared_ptr<void> small_ring; // the pinned ring of the single-batch async path (small_async.hpp), created on first use
   void sync() { SQ_HIP(hipStreamSynchronize(stream)); }
   // copies `bytes` from device to the pinned area and synchronises; returns host pointer

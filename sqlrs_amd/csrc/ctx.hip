@@ -1543,6 +1543,19 @@ int sqlrs_ctx_profile_read(sqlrs_ctx_t *ctx, int cap, const char **names, double
     }
     n++;
   }
+  // (counts of SQLRS_EXPR_FUSED_EVAL, expr_fused.hip: Filter pushes whose mask the program kernel wrote and the computed
+  //  columns of Project pushes it wrote; behind every older entry)
+  const int64_t fused_counts[2] = {ctx->fused_eval_filter_batches, ctx->fused_eval_project_columns};
+  static const char *const FUSED_COUNT_NAMES[2] = {"fused_eval_filter_batches", "fused_eval_project_columns"};
+  for (int r = 0; r < 2; r++) {
+    if (!fused_counts[r]) continue;
+    if (n < cap) {
+      names[n] = FUSED_COUNT_NAMES[r];
+      total_ms[n] = 0;
+      launches[n] = fused_counts[r];
+    }
+    n++;
+  }
   return n;
 }
 

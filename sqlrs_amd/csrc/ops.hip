@@ -22,6 +22,7 @@ struct sqlrs_filter {
   void *pin_out = nullptr;          // ... and where their kept rows land (pinned: the copy back runs at the PCIe rate)
   size_t pin_cap = 0;
   bool async_all_types = false; // sqlrs_filter_set_async_all_types: push_async's program reads Utf8 / Boolean columns too
+  bool fused_eval = false;      // SQLRS_EXPR_FUSED_EVAL at create: sqlrs_filter_push evaluates a predicate off the two fast routes in one pass (expr_fused.hip)
   ~sqlrs_filter() {
     if (pin_out) (void)hipHostFree(pin_out);
   }
@@ -105,6 +106,7 @@ int sqlrs_filter_create(sqlrs_ctx_t *ctx, const sqlrs_expr_t *expr, sqlrs_filter
     f->ctx = ctx;
     try {
       f->expr = expr_from_abi(expr);
+      f->fused_eval = (expr->reserved & SQLRS_EXPR_FUSED_EVAL) != 0;
     } catch (...) {
       delete f;
       throw;
@@ -118,7 +120,9 @@ int sqlrs_filter_create(sqlrs_ctx_t *ctx, const sqlrs_expr_t *expr, sqlrs_filter
 namespace sq {
 // mask = expr.eval_column(batch); filter_record_batch(batch, mask)  [ref: filter.rs:16-24] -> the kept rows; *sel_out
 // (optional) = the selection itself (bits + kept rows before every 4096-row tile)
-static DBatch filter_batch(sqlrs_filter *f, InBatch &ib, Selection *sel_out) {
+// `fused`: the call is sqlrs_filter_push of a filter created with SQLRS_EXPR_FUSED_EVAL — behind the two fast routes the
+// predicate is tried as one program kernel (fused_filter_selection) before the per-node evaluator
+static DBatch filter_batch(sqlrs_filter *f, InBatch &ib, Selection *sel_out, bool fused = false) {
   Ctx *ctx = f->ctx;
   auto colfn = [&](int i) -> const DCol & { return ib.col(i); };
   int64_t rows = ib.rows();
@@ -126,7 +130,7 @@ static DBatch filter_batch(sqlrs_filter *f, InBatch &ib, Selection *sel_out) {
   DCol fast_col;
   int fast_idx = -1;
   if (!filter_fast_path(ctx, f->expr, colfn, rows, &fast_idx, &sel, &fast_col) &&
-      !filter_conjunction_fast_path(ctx, f->expr, ib, rows, &sel)) {
+      !filter_conjunction_fast_path(ctx, f->expr, ib, rows, &sel) && !(fused && fused_filter_selection(ctx, f->expr, ib, &sel))) {
     DCol mask = eval_expr(ctx, f->expr, colfn, rows, false);
     mask.length = rows;
     sel = selection_from_mask(ctx, mask);
@@ -177,7 +181,7 @@ int sqlrs_filter_push(sqlrs_filter_t *f, const sqlrs_batch_t *in, int out_mem, s
     Ctx *ctx = f->ctx;
     SQ_HIP(hipSetDevice(ctx->device));
     InBatch ib(ctx, in);
-    *out = emit_batch(ctx, filter_batch(f, ib, nullptr), out_mem);
+    *out = emit_batch(ctx, filter_batch(f, ib, nullptr, f->fused_eval), out_mem);
   });
 }
 

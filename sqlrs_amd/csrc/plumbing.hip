@@ -58,6 +58,7 @@ struct sqlrs_project {
   void *pin_out = nullptr;          // ... and where their projected rows land on the host (pinned)
   size_t pin_cap = 0;
   bool async_all_types = false; // sqlrs_project_set_async_all_types: push_async's programs read Utf8 / Boolean columns too
+  bool fused_eval = false;      // SQLRS_EXPR_FUSED_EVAL at create: sqlrs_project_push evaluates the computed columns in one pass (expr_fused.hip)
   ~sqlrs_project() {
     if (pin_out) (void)hipHostFree(pin_out);
   }
@@ -184,30 +185,37 @@ int sqlrs_project_create(sqlrs_ctx_t *ctx, int num_exprs, const sqlrs_expr_t *ex
     auto p = std::unique_ptr<sqlrs_project>(new sqlrs_project());
     p->ctx = ctx;
     for (int i = 0; i < num_exprs; i++) p->exprs.push_back(expr_from_abi(&exprs[i]));
+    p->fused_eval = num_exprs > 0 && (exprs[0].reserved & SQLRS_EXPR_FUSED_EVAL) != 0;
     *out = p.release();
   });
 }
 // [ref: project.rs:14-27] a bare InputRef shares the input column's buffers (the reference clones an Arc)
-static DBatch project_batch(sqlrs_project *p, InBatch &ib, int out_mem);
+static DBatch project_batch(sqlrs_project *p, InBatch &ib, int out_mem, bool fused = false);
 int sqlrs_project_push(sqlrs_project_t *p, const sqlrs_batch_t *in, int out_mem, sqlrs_batch_t **out) {
   return guard(p->ctx, [&] {
     Ctx *ctx = p->ctx;
     SQ_HIP(hipSetDevice(ctx->device));
     InBatch ib(ctx, in);
-    *out = emit_batch(ctx, project_batch(p, ib, out_mem), out_mem);
+    *out = emit_batch(ctx, project_batch(p, ib, out_mem, p->fused_eval), out_mem);
   });
 }
 // n input batches in one call (see sqlrs_filter_push_many): small HOST batches of fixed-width columns are staged, uploaded
 // once, projected by ONE launch sequence — an expression's row i depends on row i alone (project.rs:15-27) — and cut
 // back into one HOST batch per input batch; anything else (DEVICE memory, Utf8 / Boolean columns in or out, a constant
 // projection) runs batch by batch.
-static DBatch project_batch(sqlrs_project *p, InBatch &ib, int out_mem) {
+// `fused`: the call is sqlrs_project_push of a projection created with SQLRS_EXPR_FUSED_EVAL — the computed columns are tried
+// as program kernels (fused_project_columns), all of them or none; bare InputRefs and constants are handled as ever
+static DBatch project_batch(sqlrs_project *p, InBatch &ib, int out_mem, bool fused) {
   Ctx *ctx = p->ctx;
   auto colfn = [&](int i) -> const DCol & { return ib.col(i); };
   DBatch o;
   o.rows = ib.rows();
-  for (const Expr &e : p->exprs) {
-    DCol c = eval_expr(ctx, e, colfn, ib.rows(), true);
+  std::vector<DCol> fused_cols;
+  std::vector<uint8_t> computed;
+  if (!(fused && fused_project_columns(ctx, p->exprs, ib, &fused_cols, &computed))) computed.assign(p->exprs.size(), 0);
+  for (size_t i = 0; i < p->exprs.size(); i++) {
+    const Expr &e = p->exprs[i];
+    DCol c = computed[i] ? std::move(fused_cols[i]) : eval_expr(ctx, e, colfn, ib.rows(), true);
     c.length = ib.rows();
     // a column borrowed from a caller-built DEVICE batch must not outlive the call as a view
     const bool borrowed = (c.values && !c.own_values) || (c.validity && !c.own_validity) || (c.offsets && !c.own_offsets);

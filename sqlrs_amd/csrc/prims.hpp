@@ -69,6 +69,15 @@ int64_t count_clear_bits(Ctx *ctx, const uint64_t *bits, int64_t rows);
 DCol eval_expr(Ctx *ctx, const Expr &e, const std::function<const DCol &(int)> &col, int64_t rows,
                bool materialize);
 
+// ---- whole expressions in one pass (expr_fused.hip; SQLRS_EXPR_FUSED_EVAL) ------------
+// The Filter's predicate `e` over `ib` as ONE kernel that writes the selection's mask words; true = `sel` is finished
+// (selection_finish ran).  false = the predicate is not a program (nothing launched): the caller takes eval_expr.
+bool fused_filter_selection(Ctx *ctx, const Expr &e, InBatch &ib, Selection *sel);
+// The computed columns of a projection (every expression that is not a bare InputRef / constant) by the program kernel:
+// true = (*out)[i] is column i for every i with (*computed)[i] set, the others are left to the caller.  false = some computed
+// column is not a program (nothing launched): the caller takes eval_expr for all of them.
+bool fused_project_columns(Ctx *ctx, const std::vector<Expr> &exprs, InBatch &ib, std::vector<DCol> *out, std::vector<uint8_t> *computed);
+
 // ---- key normalisation (keys.hip) ---------------------------------------------------
 // Join / group keys as one u64 per row.  Single fixed-width key column: the value itself
 // (sign-extended / bit pattern), compared exactly, NULL tracked in `validity`.  Utf8 or

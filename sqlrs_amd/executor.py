@@ -82,8 +82,12 @@ class FilterExecutor:
     """``FilterExecutor { expr, child }`` (filter.rs:7-10)."""
 
     def __init__(self, backend: abi.Backend, expr: BoundExpr, child: Iterable,
-                 out_mem: int = abi.MEM_HOST, many: int = 0, depth: int = 0, async_all_types: bool = False):
+                 out_mem: int = abi.MEM_HOST, many: int = 0, depth: int = 0, async_all_types: bool = False,
+                 fused_eval: bool = False):
         self.backend, self.expr, self.child, self.out_mem = backend, expr, child, out_mem
+        # SQLRS_EXPR_FUSED_EVAL on the predicate: sqlrs_filter_push evaluates a predicate off the two one-pass routes as one
+        # program kernel (opt-in; a backend or an older library that does not know the flag ignores the field)
+        self.fused_eval = fused_eval
         # sqlrs_filter_set_async_all_types: with depth > 0, predicates that read Utf8 / Boolean columns and batches that carry
         # Boolean columns take one launch per batch too (a backend without the entry point — the oracle — runs unchanged)
         self.async_all_types = async_all_types
@@ -116,6 +120,8 @@ class FilterExecutor:
     def execute(self):
         be = self.backend
         packed = self.expr.pack()
+        if self.fused_eval:
+            packed.abi.reserved = abi.EXPR_FUSED_EVAL
         h = C.c_void_p()
         be.check(be.fn("filter_create")(be.ctx, C.byref(packed.abi), C.byref(h)))
         try:
@@ -440,8 +446,12 @@ class ProjectExecutor:
     """``ProjectExecutor { exprs, child }`` (project.rs:6-9)."""
 
     def __init__(self, backend: abi.Backend, exprs: List[BoundExpr], child: Iterable, out_mem: int = abi.MEM_HOST,
-                 output_names: Optional[Sequence[str]] = None, many: int = 0, depth: int = 0, async_all_types: bool = False):
+                 output_names: Optional[Sequence[str]] = None, many: int = 0, depth: int = 0, async_all_types: bool = False,
+                 fused_eval: bool = False):
         self.backend, self.exprs, self.child, self.out_mem, self.output_names = backend, exprs, child, out_mem, output_names
+        # SQLRS_EXPR_FUSED_EVAL on the first expression: sqlrs_project_push evaluates the computed columns as program kernels
+        # (opt-in; see FilterExecutor)
+        self.fused_eval = fused_eval
         # sqlrs_project_set_async_all_types: with depth > 0, computed columns that read Utf8 / Boolean columns take one launch
         # per batch too (see FilterExecutor; a backend without the entry point runs unchanged)
         self.async_all_types = async_all_types
@@ -453,6 +463,8 @@ class ProjectExecutor:
     def execute(self):
         be = self.backend
         arr, keep = abi.pack_exprs(self.exprs)
+        if self.fused_eval and self.exprs:
+            arr[0].reserved = abi.EXPR_FUSED_EVAL
         h = C.c_void_p()
         be.check(be.fn("project_create")(be.ctx, len(self.exprs), arr, C.byref(h)))
         try:
