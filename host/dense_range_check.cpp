@@ -1,5 +1,6 @@
 // Stand-alone check of dense_range_decide (sqlrs_amd/csrc/dense_range.hpp): the one decision whether a build side's key
-// range takes the join's direct-address table.  No HIP: built by tests/test_join_model_cpu.py with
+// range takes the join's direct-address table — and of dense_verdict_decide beside it: what the finished attempt says about the
+// build side (adopt / not unique / dup range usable).  No HIP: built by tests/test_join_model_cpu.py with
 //   g++ -std=c++17 -fsanitize=address,undefined -I sqlrs_amd/csrc host/dense_range_check.cpp
 // and run; exit status 0 = every row of the table below holds.  `lo`, `hi` are ORDERED images (0 = INT64_MIN, ~0 = INT64_MAX).
 #include "dense_range.hpp"
@@ -44,6 +45,32 @@ int main() {
                   r.lo, r.hi, r.max_range, (int)d.ok, d.range, (int)r.ok, r.range);
     }
   }
-  std::printf("%d of %d rows failed\n", bad, (int)(sizeof(rows) / sizeof(rows[0])));
+  // dense_verdict_decide: what the finished attempt says about a 1 000-row build side whose valid keys lie in [lo, hi]
+  const struct {
+    const char *what;
+    uint64_t lo, hi, occupied, nulls, rows;
+    bool had_validity, adopt, not_unique, dup_range;
+  } verdicts[] = {
+      {"unique, no NULL", 100, 1099, 1000, 0, 1000, false, true, false, false},
+      {"unique, a bitmap without NULLs", 100, 1099, 1000, 0, 1000, true, true, false, false},
+      {"exactly one NULL key: adopted", 100, 1098, 999, 1, 1000, true, true, false, false},
+      {"two NULL keys match each other: not unique, no dup range", 100, 1097, 998, 2, 1000, true, false, true, false},
+      {"duplicates, no NULL: dup range", 100, 599, 500, 0, 1000, false, false, true, true},
+      {"duplicates under a bitmap with zero NULLs: no dup range", 100, 599, 500, 0, 1000, true, false, true, false},
+      {"duplicates and one NULL: no dup range", 100, 598, 499, 1, 1000, true, false, true, false},
+      {"range refused (max_range + 1): nothing known", 0, MR, 1000, 0, 1000, false, false, false, false},
+      {"range refused, duplicates: nothing known", 0, ALL, 500, 0, 1000, false, false, false, false},
+      {"lo > hi (every key NULL, one row): nothing known", ALL, 0, 0, 1, 1, true, false, false, false},
+      {"lo > hi, 1 000 NULL keys: nothing known", ALL, 0, 0, 1000, 1000, true, false, false, false},
+  };
+  for (const auto &r : verdicts) {
+    const DenseVerdict v = dense_verdict_decide(dense_range_decide(r.lo, r.hi, MR), r.occupied, r.nulls, r.rows, r.had_validity);
+    if (v.adopt != r.adopt || v.not_unique != r.not_unique || v.dup_range != r.dup_range) {
+      bad++;
+      std::printf("FAIL %s: adopt %d not_unique %d dup_range %d, expected %d %d %d\n", r.what, (int)v.adopt, (int)v.not_unique,
+                  (int)v.dup_range, (int)r.adopt, (int)r.not_unique, (int)r.dup_range);
+    }
+  }
+  std::printf("%d of %d rows failed\n", bad, (int)(sizeof(rows) / sizeof(rows[0]) + sizeof(verdicts) / sizeof(verdicts[0])));
   return bad ? 1 : 0;
 }

@@ -25,13 +25,11 @@
 #include "join_kernels.hpp"
 #include "key_hash.hpp"
 #include "join_state.hpp"
+#include "radix_part.hpp"
 
 #include "join_probe_kernels.hpp" // every kernel of this operator (namespace sq)
 
 using namespace sq;
-
-#include "join_state.hpp"
-#include "radix_part.hpp"
 
 extern "C" void sqlrs_batch_release(sqlrs_batch_t *batch);
 
@@ -45,6 +43,28 @@ struct Pairs {
   // joined batch is the probe batch itself, nothing to gather
   bool right_identity = false;
 };
+// the index pairs as two columns: u64 build rows (NULL where an outer join's probe row has no partner), u32 probe rows
+static void pairs_as_columns(const Pairs &p, DCol *l, DCol *r) {
+  l->dtype = SQLRS_UINT64;
+  l->length = p.m;
+  l->values = p.left->p;
+  l->own_values = p.left;
+  if (p.left_validity) {
+    l->validity = p.left_validity->as<uint64_t>();
+    l->own_validity = p.left_validity;
+    l->null_count = -1;
+  }
+  r->dtype = SQLRS_UINT32;
+  r->length = p.m;
+  r->values = p.right->p;
+  r->own_values = p.right;
+}
+
+static Slot *slots_of(const sqlrs_hash_join *j) { return j->table ? j->table->as<Slot>() : nullptr; }
+static bool is_outer_right(const sqlrs_hash_join *j) { return j->join_type == SQLRS_JOIN_RIGHT || j->join_type == SQLRS_JOIN_FULL; }
+// (both take the RESULT of hook("SQLRS_..."))
+static bool hook_is_zero(const char *e) { return e && std::atoi(e) == 0; }
+static int hook_int(const char *e, int unset) { return e ? std::atoi(e) : unset; }
 
 static std::vector<DCol> eval_key_cols(Ctx *ctx, const std::vector<Expr> &exprs, const std::function<const DCol &(int)> &col,
                                        int64_t rows) {
@@ -65,49 +85,6 @@ static NKeys eval_keys(Ctx *ctx, const std::vector<Expr> &exprs,
 // composite key, which also makes dense key grids eligible for the direct-address table and sparse ones for the LDS route.
 // NULL in a key column never matches here; the composite is taken only when no build key is NULL, and a probe row with a NULL
 // key, a value outside the build side's ranges, or a key column of another integer type gets a key that matches nothing.
-struct CompJoinKeys {
-  const void *vals[4];
-  const uint64_t *valid[4];
-  int64_t min[4];
-  uint64_t range[4], stride[4];
-  int is32[4];
-  int nk; // < 0: every row gets the no-match key (key column types differ between the sides)
-};
-constexpr uint64_t COMP_NO_MATCH = ~0ull; // (composites are < 2^62)
-__device__ __forceinline__ int64_t comp_value(const CompJoinKeys &ck, int c, int64_t i) {
-  return ck.is32[c] ? (int64_t)((const int32_t *)ck.vals[c])[i] : ((const int64_t *)ck.vals[c])[i];
-}
-__global__ __launch_bounds__(256) void comp_join_minmax_kernel(const void *__restrict__ vals, int is32, int64_t n, long long *mm) {
-  long long lo = INT64_MAX, hi = INT64_MIN;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const long long v = is32 ? (long long)((const int32_t *)vals)[i] : ((const long long *)vals)[i];
-    lo = min(lo, v);
-    hi = max(hi, v);
-  }
-  for (int m = 32; m >= 1; m >>= 1) {
-    lo = min(lo, (long long)shfl_xor_u64((uint64_t)lo, m));
-    hi = max(hi, (long long)shfl_xor_u64((uint64_t)hi, m));
-  }
-  if (lane_id() == 0) {
-    atomicMin(mm, lo);
-    atomicMax(mm + 1, hi);
-  }
-}
-__global__ __launch_bounds__(256) void comp_join_keys_kernel(CompJoinKeys ck, int64_t n, uint64_t *__restrict__ out) {
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  uint64_t key = 0;
-  bool ok = ck.nk > 0;
-  for (int c = 0; c < ck.nk && ok; c++) {
-    if (ck.valid[c] && !((ck.valid[c][i >> 6] >> (i & 63)) & 1ull)) ok = false;
-    else {
-      const uint64_t d = (uint64_t)comp_value(ck, c, i) - (uint64_t)ck.min[c]; // (wraps to a huge value below the minimum)
-      if (d >= ck.range[c]) ok = false;
-      else key += d * ck.stride[c];
-    }
-  }
-  out[i] = ok ? key : COMP_NO_MATCH;
-}
 // build side: ranges of the key columns over all build batches -> j->comp, and the composite key of every build row
 static BufP composite_build_keys(sqlrs_hash_join *j) {
   Ctx *ctx = j->ctx;
@@ -213,58 +190,9 @@ static NKeys composite_probe_keys(sqlrs_hash_join *j, const std::function<const 
   return k;
 }
 
-static void build_hash_table(sqlrs_hash_join *j);
-static bool build_dense_dup(sqlrs_hash_join *j);
-// The direct-address build's verdict (dense_pack_count_kernel: st[0 .. 35)) -> the join's state; what is not a unique dense
-// key set goes on to the general table.  `h`: the words when the caller has fetched them already (with its own answer, in
-// one round trip), else they are fetched here.
-void dense_resolve(sqlrs_hash_join *j, const uint64_t *h) { // (join_state.hpp: join_async.hip resolves too)
-  if (!j->dense_pending) return;
+// ---- build: key parts -> j->bkeys, j->bkeys_validity (kept for the fused join+aggregate route, hashagg_op.hip), j->exact, j->key_dtype
+static void concat_build_keys(sqlrs_hash_join *j) {
   Ctx *ctx = j->ctx;
-  j->dense_pending = false;
-  const int64_t n = j->nB;
-  uint64_t hw[DENSE_ST_WORDS];
-  std::memcpy(hw, h ? h : (const uint64_t *)ctx->fetch(j->pend_st->p, 8 * DENSE_ST_WORDS), sizeof(hw)); // (later fetches reuse the staging buffer)
-  BufP dense = std::move(j->pend_dense), packed = std::move(j->pend_packed);
-  j->pend_st = nullptr;
-  uint64_t nlo = 0, hi = 0;
-  for (int i = 0; i < DENSE_MM; i++) nlo = std::max(nlo, hw[i]), hi = std::max(hi, hw[DENSE_MM + i]);
-  const uint64_t lo = ~nlo, occupied = hw[2 * DENSE_MM], nulls = hw[2 * DENSE_MM + 1];
-  const uint32_t null_head = (uint32_t)hw[2 * DENSE_MM + 2];
-  const DenseRange dr = dense_range_decide(lo, hi, j->pend_max_range); // (what dense_dev decided)
-  const uint64_t range = dr.range;
-  if (dr.ok) {
-    const uint64_t dmin = lo ^ (1ull << 63);
-    if (nulls <= 1 && occupied + nulls == (uint64_t)n) {
-      ctx->join_route[Ctx::JR_DENSE_ADOPTED]++;
-      j->unique = true;
-      j->unique_known = j->table_built = true;
-      j->dense = dense;
-      j->dense_min = dmin;
-      j->dense_range = range;
-      j->dense_null_head = null_head;
-      j->dense_packed = packed;
-      j->dense_pbits = j->pend_bits;
-      return;
-    }
-    // fewer occupied slots than valid keys (or several NULL keys, which match each other): the build keys are NOT
-    // unique — a fact the fused join+aggregate need not discover again by inserting them into its bucket tables
-    j->unique = false;
-    j->unique_known = true;
-    if (nulls == 0 && !j->pend_validity) { // (no NULL key: the fused join+aggregate can take multiplicities per key, hash_join_dup_mult)
-      j->dup_min = dmin;
-      j->dup_range = range;
-    }
-  }
-  ctx->join_route[Ctx::JR_DENSE_REFUSED]++;
-  if (j->lazy_table) return; // built by hash_join_ensure_table when something probes it
-  if (build_dense_dup(j)) return; // duplicate keys over a dense range: runs by key, no general table
-  if (lds_build_first(j)) return; // general keys on LDS tables: uniqueness from there, the global table on first need only
-  build_hash_table(j);
-}
-static void build_table(sqlrs_hash_join *j) {
-  Ctx *ctx = j->ctx;
-  // concat key parts
   int64_t n = j->nB;
   // one build batch (the usual case): its normalised keys ARE the key array, no concat copy
   BufP ckeys = composite_build_keys(j); // several integer key columns: one exact key (or null: as normalised per batch)
@@ -278,7 +206,6 @@ static void build_table(sqlrs_hash_join *j) {
   j->key_dtype = ckeys ? SQLRS_INT64 : j->left_key_parts[0].dtype;
   if (!ckeys) {
     size_t off = 0;
-    std::vector<DCol> vparts;
     for (const NKeys &p : j->left_key_parts) {
       if (p.exact != j->exact || p.dtype != j->key_dtype)
         fail(SQLRS_ERR_ARROW, "join key type changed between build batches");
@@ -311,136 +238,175 @@ static void build_table(sqlrs_hash_join *j) {
         validity = c.own_validity;
     }
   }
-  j->bkeys = keys; // kept for the fused join+aggregate route (hashagg_op.hip)
+  j->bkeys = keys;
   j->bkeys_validity = validity;
-  // 1. dense surrogate keys (range <= 4 x rows — 16 x for a join+aggregate's join — and < 2^31) -> direct-address table.  It is tried
-  //    first: when the build keys turn out unique nothing else is needed, and the 16-byte-slot
-  //    hash table (1.1 ms for 1e7 keys) is never built.
-  const char *db1_e = hook("SQLRS_DENSE_BUILD_ONE_FETCH"); // A/B hook, read per call (0 = the two-fetch sequence below)
-  // (the one-fetch form allocates the table of the LARGEST admissible range before it has looked at a key: only while that
-  //  stays under 1 GiB — advisor r05; beyond, the two-fetch sequence below sizes the table from the range it has seen)
-  const uint64_t spk1 = j->lazy_table ? DENSE_SLOTS_PER_KEY_OWNED : 4;
-  if (j->exact && n > 0 && n <= (1ll << 24) && 4 * (spk1 * (uint64_t)n + 1024) <= (1ull << 30) && j->key_dtype != SQLRS_FLOAT64 &&
-      !(db1_e && std::atoi(db1_e) == 0)) {
-    // one fetch (see dense_pack_count_kernel): the table is sized for the largest range that takes the route
-    ProfScope ps(ctx, "join_build_dense");
-    const char *pj_e = hook("SQLRS_DENSE_JOIN_SLOTS_PLAIN"); // tuning hook, read per call
-    const uint64_t slots_per_key = j->lazy_table ? DENSE_SLOTS_PER_KEY_OWNED : (pj_e ? (uint64_t)std::max(1, std::atoi(pj_e)) : 4);
-    const uint64_t max_range = slots_per_key * (uint64_t)n + 1024;
-    uint32_t bits = 1;
-    while (((1ull << bits) - 1) < (uint64_t)n) bits++; // all ones = empty must not be a build row
-    const char *pk_e = hook("SQLRS_DENSE_PACKED"); // A/B hook, read per call (0 = the probe reads the 4-byte table)
-    if (bits < 8) bits = 8;
-    if (bits > 25 || (max_range + 2) * bits >= (1ull << 32) || j->lazy_table || (pk_e && std::atoi(pk_e) == 0)) bits = 0;
-    BufP st = ctx->alloc_zero(8 * (DENSE_ST_WORDS + 1)); // (+ the miss flag of a first probe that runs before the verdict is fetched)
-    BufP dense = ctx->alloc(4 * (size_t)max_range + 64);
-    BufP packed = bits ? ctx->alloc(4 * (size_t)((max_range + 2 + 31) / 32) * bits + 16) : nullptr;
-    const uint64_t *vp = validity ? validity->as<uint64_t>() : nullptr;
-    unsigned long long *stp = st->as<unsigned long long>();
-    const unsigned mblocks = (unsigned)std::min<int64_t>(ceil_div(n, 256 * 8), 4 * (int64_t)ctx->num_cus);
-    const bool init_fused = max_range + 2 <= (8ull << 20); // (entries: <= 32 MiB of table)
-    key_minmax_inv_kernel<<<dim3(mblocks), dim3(256), 0, ctx->stream>>>(keys->as<uint64_t>(), vp, n, stp, init_fused ? dense->as<uint4>() : nullptr,
-                                                                        (int64_t)((max_range + 2 + 3) / 4));
-    if (!init_fused) {
-      const unsigned iblocks = (unsigned)std::min<int64_t>(ceil_div((int64_t)max_range + 2, 256 * 4 * 4), 4 * (int64_t)ctx->num_cus);
-      dense_init_dev_kernel<<<dim3(iblocks), dim3(256), 0, ctx->stream>>>(stp, max_range, dense->as<uint4>());
-    }
-    if (n < (1ll << 21))
-      dense_fill_dev_kernel<4><<<dim3((unsigned)ceil_div(n, 256 * 4)), dim3(256), 0, ctx->stream>>>(keys->as<uint64_t>(), vp, n, stp, max_range,
-                                                                                                  dense->as<uint32_t>(), stp + 2 * DENSE_MM);
-    else
-      dense_fill_dev_kernel<1><<<dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream>>>(keys->as<uint64_t>(), vp, n, stp, max_range,
-                                                                                              dense->as<uint32_t>(), stp + 2 * DENSE_MM);
-    if (bits) {
-      const unsigned pblocks = (unsigned)std::min<int64_t>(ceil_div(ceil_div((int64_t)max_range + 2, 32), 256), 8 * (int64_t)ctx->num_cus);
-      dense_pack_count_kernel<<<dim3(pblocks), dim3(256), 0, ctx->stream>>>(dense->as<uint32_t>(), stp, max_range, bits,
-                                                                          packed->as<uint32_t>(), stp + 2 * DENSE_MM);
-    } else {
-      const unsigned cblocks = (unsigned)std::min<int64_t>(ceil_div((int64_t)max_range, 256 * 8), 4 * (int64_t)ctx->num_cus);
-      dense_count_dev_kernel<<<dim3(cblocks), dim3(256), 0, ctx->stream>>>(dense->as<uint32_t>(), stp, max_range, stp + 2 * DENSE_MM);
-    }
-    SQ_HIP(hipGetLastError());
-    ctx->join_route[Ctx::JR_DENSE_ONE_FETCH]++;
-    ctx->join_route[bits ? Ctx::JR_DENSE_PACKED : Ctx::JR_DENSE_PLAIN]++;
-    j->dense_pending = true;
-    j->pend_st = st;
-    j->pend_dense = dense;
-    j->pend_packed = packed;
-    j->pend_bits = bits;
-    j->pend_max_range = max_range;
-    j->pend_validity = validity != nullptr;
-    // The verdict stays on the device when the first probe can take it from there (dense_resolve): a plain join whose probe
-    // kernels read the packed table.  SQLRS_DENSE_BUILD_DEFER=0 (read per call): decide here.
-    const char *df_e = hook("SQLRS_DENSE_BUILD_DEFER");
-    if (bits && !j->lazy_table && !(df_e && std::atoi(df_e) == 0)) return;
-    dense_resolve(j);
-    return;
-  } else if (j->exact && n > 0 && j->key_dtype != SQLRS_FLOAT64) {
-    BufP mm = ctx->alloc(16); // {min = ~0, max = 0} without a host round trip
-    SQ_HIP(hipMemsetAsync(mm->p, 0xff, 8, ctx->stream));
-    SQ_HIP(hipMemsetAsync(mm->as<uint8_t>() + 8, 0, 8, ctx->stream));
-    const uint64_t *vp = validity ? validity->as<uint64_t>() : nullptr;
-    unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(n, 256 * 8), 4 * (int64_t)ctx->num_cus);
-    key_minmax_kernel<<<dim3(blocks), dim3(256), 0, ctx->stream>>>(keys->as<uint64_t>(), vp, n,
-                                                                  mm->as<unsigned long long>(),
-                                                                  mm->as<unsigned long long>() + 1);
-    SQ_HIP(hipGetLastError());
-    const uint64_t *h = (const uint64_t *)ctx->fetch(mm->p, 16);
-    uint64_t lo = h[0], hi = h[1];
-    ctx->join_route[Ctx::JR_DENSE_TWO_FETCH]++;
-    ctx->join_route[Ctx::JR_DENSE_REFUSED]++; // (taken back where the table is adopted)
-    if (lo <= hi) {
-      // ordered images differ like the signed values
-      // (a join owned by a HashJoin+HashAgg takes the table up to 16 slots per key: its fused route then partitions
-      //  by key range and needs only the existence bitmap of the range — a filtered dimension, or the hash-partitioned
-      //  shard of one that a rank of the multi-GPU plan receives, 1/8 of the keys of the range for 8 ranks)
-      const char *pj_e = hook("SQLRS_DENSE_JOIN_SLOTS_PLAIN"); // tuning hook, read per call
-      const uint64_t slots_per_key = j->lazy_table ? DENSE_SLOTS_PER_KEY_OWNED : (pj_e ? (uint64_t)std::max(1, std::atoi(pj_e)) : 4);
-      const DenseRange dr = dense_range_decide(lo, hi, slots_per_key * (uint64_t)n + 1024);
-      const uint64_t range = dr.range;
-      if (dr.ok) {
-        ProfScope ps(ctx, "join_build_dense");
-        BufP dense = ctx->alloc(4 * (size_t)range + 8);
-        SQ_HIP(hipMemsetAsync(dense->p, 0xff, 4 * (size_t)range + 8, ctx->stream));
-        uint64_t dmin = lo ^ (1ull << 63); // back from the ordered image to the two's complement bits
-        uint32_t *null_head = dense->as<uint32_t>() + range; // spare slot after the table
-        BufP cnt = ctx->alloc_zero(24); // {occupied slots, NULL keys, copy of the NULL row's head (u32)}
-        dense_fill_kernel<<<dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream>>>(
-            keys->as<uint64_t>(), vp, n, dmin, dense->as<uint32_t>(), null_head, cnt->as<unsigned long long>());
-        unsigned cblocks = (unsigned)std::min<int64_t>(ceil_div((int64_t)range, 256 * 8), 4 * (int64_t)ctx->num_cus);
-        dense_count_kernel<<<dim3(cblocks), dim3(256), 0, ctx->stream>>>(dense->as<uint32_t>(), (int64_t)range,
-                                                                        cnt->as<unsigned long long>());
-        SQ_HIP(hipMemcpyAsync(cnt->as<uint64_t>() + 2, null_head, 4, hipMemcpyDeviceToDevice, ctx->stream));
-        SQ_HIP(hipGetLastError());
-        const uint64_t *hc = (const uint64_t *)ctx->fetch(cnt->p, 24); // one round trip for all three
-        const uint32_t hd[2] = {(hc[1] <= 1 && hc[0] + hc[1] == (uint64_t)n) ? 0u : 1u, (uint32_t)hc[2]};
-        ctx->join_route[Ctx::JR_DENSE_PLAIN]++;
-        if (hd[0] == 0) {
-          ctx->join_route[Ctx::JR_DENSE_REFUSED]--;
-          ctx->join_route[Ctx::JR_DENSE_ADOPTED]++;
-          j->unique = true;
-          j->unique_known = j->table_built = true;
-          j->dense = dense;
-          j->dense_min = dmin;
-          j->dense_range = range;
-          j->dense_null_head = hd[1];
-          return;
-        }
-        // fewer occupied slots than valid keys (or several NULL keys, which match each other): the build keys are NOT
-        // unique — a fact the fused join+aggregate need not discover again by inserting them into its bucket tables
-        j->unique = false;
-        j->unique_known = true;
-        if (hc[1] == 0 && !validity) { // (no NULL key: the fused join+aggregate can take multiplicities per key, hash_join_dup_mult)
-          j->dup_min = dmin;
-          j->dup_range = range;
-        }
-      }
-    }
-  }
+}
+
+static void build_hash_table(sqlrs_hash_join *j);
+static bool build_dense_dup(sqlrs_hash_join *j);
+// a build side without a direct-address table (not tried, or refused)
+static void build_after_refusal(sqlrs_hash_join *j) {
   if (j->lazy_table) return; // built by hash_join_ensure_table when something probes it
   if (build_dense_dup(j)) return; // duplicate keys over a dense range: runs by key, no general table
   if (lds_build_first(j)) return; // general keys on LDS tables: uniqueness from there, the global table on first need only
   build_hash_table(j);
+}
+// direct-address slots per build key (a join owned by a HashJoin+HashAgg takes the table up to 16 slots per key: its fused route
+// then partitions by key range and needs only the existence bitmap of the range — a filtered dimension, or the hash-partitioned
+// shard of one that a rank of the multi-GPU plan receives, 1/8 of the keys of the range for 8 ranks)
+static uint64_t dense_slots_per_key(const sqlrs_hash_join *j) {
+  if (j->lazy_table) return DENSE_SLOTS_PER_KEY_OWNED;
+  return (uint64_t)std::max(1, hook_int(hook("SQLRS_DENSE_JOIN_SLOTS_PLAIN"), 4)); // tuning hook, read per call
+}
+// the table of a direct-address attempt over [dmin, dmin + range) (empty: the range was refused before one was built)
+struct DenseBuilt {
+  uint64_t dmin = 0, range = 0;
+  BufP dense, packed;
+  uint32_t bits = 0, null_head = 0xffffffffu;
+};
+// A verdict (dense_verdict_decide, dense_range.hpp) -> the join's state and ONE of JR_DENSE_ADOPTED / JR_DENSE_REFUSED per
+// attempt.  true = adopted, the build is done; false: the caller goes on with build_after_refusal.
+static bool dense_apply_verdict(sqlrs_hash_join *j, const DenseVerdict &v, const DenseBuilt &t) {
+  j->ctx->join_route[v.adopt ? Ctx::JR_DENSE_ADOPTED : Ctx::JR_DENSE_REFUSED]++;
+  if (v.adopt) {
+    j->unique = j->unique_known = j->table_built = true;
+    j->dense = t.dense;
+    j->dense_min = t.dmin;
+    j->dense_range = t.range;
+    j->dense_null_head = t.null_head;
+    j->dense_packed = t.packed;
+    j->dense_pbits = t.bits;
+    return true;
+  }
+  if (v.not_unique) {
+    // fewer occupied slots than valid keys (or several NULL keys, which match each other): the build keys are NOT
+    // unique — a fact the fused join+aggregate need not discover again by inserting them into its bucket tables
+    j->unique = false;
+    j->unique_known = true;
+  }
+  if (v.dup_range) { // (no NULL key: the fused join+aggregate can take multiplicities per key, hash_join_dup_mult)
+    j->dup_min = t.dmin;
+    j->dup_range = t.range;
+  }
+  return false;
+}
+// The one-fetch build's verdict (dense_pack_count_kernel: st[0 .. 35)) -> the join's state.  `h`: the words when the caller
+// has fetched them already (with its own answer, in one round trip), else they are fetched here.
+void dense_resolve(sqlrs_hash_join *j, const uint64_t *h) { // (join_state.hpp: join_async.hip resolves too)
+  if (!j->dense_pending) return;
+  j->dense_pending = false;
+  uint64_t hw[DENSE_ST_WORDS];
+  std::memcpy(hw, h ? h : (const uint64_t *)j->ctx->fetch(j->pend_st->p, 8 * DENSE_ST_WORDS), sizeof(hw)); // (later fetches reuse the staging buffer)
+  j->pend_st = nullptr;
+  uint64_t nlo = 0, hi = 0;
+  for (int i = 0; i < DENSE_MM; i++) nlo = std::max(nlo, hw[i]), hi = std::max(hi, hw[DENSE_MM + i]);
+  const uint64_t lo = ~nlo, occupied = hw[2 * DENSE_MM], nulls = hw[2 * DENSE_MM + 1];
+  const DenseRange dr = dense_range_decide(lo, hi, j->pend_max_range); // (what dense_dev decided)
+  const DenseVerdict v = dense_verdict_decide(dr, occupied, nulls, (uint64_t)j->nB, j->pend_validity);
+  const DenseBuilt t{lo ^ (1ull << 63), dr.range, std::move(j->pend_dense), std::move(j->pend_packed), j->pend_bits, (uint32_t)hw[2 * DENSE_MM + 2]};
+  if (!dense_apply_verdict(j, v, t)) build_after_refusal(j);
+}
+// 1. dense surrogate keys (range <= 4 x rows — 16 x for a join+aggregate's join — and < 2^31) -> direct-address table.  It is tried
+//    first: when the build keys turn out unique nothing else is needed, and the 16-byte-slot hash table (1.1 ms for 1e7 keys) is never built.
+// One fetch (see dense_pack_count_kernel): the table is sized for the largest range that takes the route.  false: not taken.
+static bool dense_try_one_fetch(sqlrs_hash_join *j) {
+  Ctx *ctx = j->ctx;
+  const int64_t n = j->nB;
+  // (the one-fetch form allocates the table of the LARGEST admissible range before it has looked at a key: only while that
+  //  stays under 1 GiB — advisor r05; beyond, the two-fetch sequence sizes the table from the range it has seen)
+  const uint64_t spk1 = j->lazy_table ? DENSE_SLOTS_PER_KEY_OWNED : 4;
+  if (n > (1ll << 24) || 4 * (spk1 * (uint64_t)n + 1024) > (1ull << 30)) return false;
+  if (hook_is_zero(hook("SQLRS_DENSE_BUILD_ONE_FETCH"))) return false; // A/B hook, read per call (0 = the two-fetch sequence below)
+  ProfScope ps(ctx, "join_build_dense");
+  const uint64_t max_range = dense_slots_per_key(j) * (uint64_t)n + 1024;
+  uint32_t bits = 1;
+  while (((1ull << bits) - 1) < (uint64_t)n) bits++; // all ones = empty must not be a build row
+  if (bits < 8) bits = 8;
+  if (bits > 25 || (max_range + 2) * bits >= (1ull << 32) || j->lazy_table) bits = 0;
+  if (hook_is_zero(hook("SQLRS_DENSE_PACKED"))) bits = 0; // A/B hook, read per call (0 = the probe reads the 4-byte table)
+  BufP st = ctx->alloc_zero(8 * (DENSE_ST_WORDS + 1)); // (+ the miss flag of a first probe that runs before the verdict is fetched)
+  BufP dense = ctx->alloc(4 * (size_t)max_range + 64);
+  BufP packed = bits ? ctx->alloc(4 * (size_t)((max_range + 2 + 31) / 32) * bits + 16) : nullptr;
+  const uint64_t *keys = j->bkeys->as<uint64_t>(), *vp = j->bkeys_validity ? j->bkeys_validity->as<uint64_t>() : nullptr;
+  unsigned long long *stp = st->as<unsigned long long>();
+  const unsigned mblocks = (unsigned)std::min<int64_t>(ceil_div(n, 256 * 8), 4 * (int64_t)ctx->num_cus);
+  const bool init_fused = max_range + 2 <= (8ull << 20); // (entries: <= 32 MiB of table)
+  key_minmax_inv_kernel<<<dim3(mblocks), dim3(256), 0, ctx->stream>>>(keys, vp, n, stp, init_fused ? dense->as<uint4>() : nullptr,
+                                                                      (int64_t)((max_range + 2 + 3) / 4));
+  if (!init_fused) {
+    const unsigned iblocks = (unsigned)std::min<int64_t>(ceil_div((int64_t)max_range + 2, 256 * 4 * 4), 4 * (int64_t)ctx->num_cus);
+    dense_init_dev_kernel<<<dim3(iblocks), dim3(256), 0, ctx->stream>>>(stp, max_range, dense->as<uint4>());
+  }
+  if (n < (1ll << 21))
+    dense_fill_dev_kernel<4><<<dim3((unsigned)ceil_div(n, 256 * 4)), dim3(256), 0, ctx->stream>>>(keys, vp, n, stp, max_range,
+                                                                                                dense->as<uint32_t>(), stp + 2 * DENSE_MM);
+  else
+    dense_fill_dev_kernel<1><<<dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream>>>(keys, vp, n, stp, max_range,
+                                                                                            dense->as<uint32_t>(), stp + 2 * DENSE_MM);
+  if (bits) {
+    const unsigned pblocks = (unsigned)std::min<int64_t>(ceil_div(ceil_div((int64_t)max_range + 2, 32), 256), 8 * (int64_t)ctx->num_cus);
+    dense_pack_count_kernel<<<dim3(pblocks), dim3(256), 0, ctx->stream>>>(dense->as<uint32_t>(), stp, max_range, bits,
+                                                                        packed->as<uint32_t>(), stp + 2 * DENSE_MM);
+  } else {
+    const unsigned cblocks = (unsigned)std::min<int64_t>(ceil_div((int64_t)max_range, 256 * 8), 4 * (int64_t)ctx->num_cus);
+    dense_count_dev_kernel<<<dim3(cblocks), dim3(256), 0, ctx->stream>>>(dense->as<uint32_t>(), stp, max_range, stp + 2 * DENSE_MM);
+  }
+  SQ_HIP(hipGetLastError());
+  ctx->join_route[Ctx::JR_DENSE_ONE_FETCH]++;
+  ctx->join_route[bits ? Ctx::JR_DENSE_PACKED : Ctx::JR_DENSE_PLAIN]++;
+  j->dense_pending = true;
+  j->pend_st = st;
+  j->pend_dense = dense;
+  j->pend_packed = packed;
+  j->pend_bits = bits;
+  j->pend_max_range = max_range;
+  j->pend_validity = j->bkeys_validity != nullptr;
+  // The verdict stays on the device when the first probe can take it from there (dense_resolve): a plain join whose probe
+  // kernels read the packed table.  SQLRS_DENSE_BUILD_DEFER=0 (read per call): decide here.
+  if (hook_is_zero(hook("SQLRS_DENSE_BUILD_DEFER")) || !bits || j->lazy_table) dense_resolve(j); // A/B hook, read per call
+  return true;
+}
+// Two fetches: the key range first, then a table of exactly that range and its fill / count.  true = adopted, the build is done.
+static bool dense_try_two_fetch(sqlrs_hash_join *j) {
+  Ctx *ctx = j->ctx;
+  const int64_t n = j->nB;
+  BufP mm = ctx->alloc(16); // {min = ~0, max = 0} without a host round trip
+  SQ_HIP(hipMemsetAsync(mm->p, 0xff, 8, ctx->stream));
+  SQ_HIP(hipMemsetAsync(mm->as<uint8_t>() + 8, 0, 8, ctx->stream));
+  const uint64_t *keys = j->bkeys->as<uint64_t>(), *vp = j->bkeys_validity ? j->bkeys_validity->as<uint64_t>() : nullptr;
+  unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(n, 256 * 8), 4 * (int64_t)ctx->num_cus);
+  key_minmax_kernel<<<dim3(blocks), dim3(256), 0, ctx->stream>>>(keys, vp, n, mm->as<unsigned long long>(),
+                                                                mm->as<unsigned long long>() + 1);
+  SQ_HIP(hipGetLastError());
+  const uint64_t *h = (const uint64_t *)ctx->fetch(mm->p, 16);
+  const uint64_t lo = h[0], hi = h[1]; // ordered images differ like the signed values; lo > hi: no valid key
+  ctx->join_route[Ctx::JR_DENSE_TWO_FETCH]++;
+  const DenseRange dr = lo <= hi ? dense_range_decide(lo, hi, dense_slots_per_key(j) * (uint64_t)n + 1024) : DenseRange{false, 0};
+  if (!dr.ok) return dense_apply_verdict(j, dense_verdict_decide(dr, 0, 0, (uint64_t)n, vp != nullptr), DenseBuilt{}); // refused: no table, nothing known
+  const uint64_t range = dr.range, dmin = lo ^ (1ull << 63); // (back from the ordered image to the two's complement bits)
+  ProfScope ps(ctx, "join_build_dense");
+  BufP dense = ctx->alloc(4 * (size_t)range + 8);
+  SQ_HIP(hipMemsetAsync(dense->p, 0xff, 4 * (size_t)range + 8, ctx->stream));
+  uint32_t *null_head = dense->as<uint32_t>() + range; // spare slot after the table
+  BufP cnt = ctx->alloc_zero(24); // {occupied slots, NULL keys, copy of the NULL row's head (u32)}
+  dense_fill_kernel<<<dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream>>>(
+      keys, vp, n, dmin, dense->as<uint32_t>(), null_head, cnt->as<unsigned long long>());
+  unsigned cblocks = (unsigned)std::min<int64_t>(ceil_div((int64_t)range, 256 * 8), 4 * (int64_t)ctx->num_cus);
+  dense_count_kernel<<<dim3(cblocks), dim3(256), 0, ctx->stream>>>(dense->as<uint32_t>(), (int64_t)range,
+                                                                  cnt->as<unsigned long long>());
+  SQ_HIP(hipMemcpyAsync(cnt->as<uint64_t>() + 2, null_head, 4, hipMemcpyDeviceToDevice, ctx->stream));
+  SQ_HIP(hipGetLastError());
+  const uint64_t *hc = (const uint64_t *)ctx->fetch(cnt->p, 24); // one round trip for all three
+  ctx->join_route[Ctx::JR_DENSE_PLAIN]++;
+  return dense_apply_verdict(j, dense_verdict_decide(dr, hc[0], hc[1], (uint64_t)n, vp != nullptr), {dmin, range, dense, nullptr, 0, (uint32_t)hc[2]});
+}
+static void build_table(sqlrs_hash_join *j) {
+  concat_build_keys(j);
+  if (j->exact && j->nB > 0 && j->key_dtype != SQLRS_FLOAT64) {
+    if (dense_try_one_fetch(j)) return; // verdict pending on the device, or resolved (dense_resolve goes on after a refusal)
+    if (dense_try_two_fetch(j)) return; // adopted
+  }
+  build_after_refusal(j);
 }
 
 // 1b. (round 6) DUPLICATE build keys over a dense range — a foreign key joined to a foreign key, a dimension attribute: the direct-
@@ -450,127 +416,6 @@ static void build_table(sqlrs_hash_join *j) {
 // (hash_join_dup_mult), an exclusive scan, and the rows stably sorted by (key - min) ARE the runs; the probe's count pass reads
 // {run start, rows} with one 8-byte load per probe row from a table the size of the range (L2-resident for C3's shapes) instead
 // of three passes over LDS tables.  1e8 x 1e6 rows, every key ~4 times (4e8 pairs), build + probe: 3.76 -> 2.57 ms.
-// the run starts with three entries behind the range: start[range] = rows (the end of the last run), start[range + 1] =
-// start[range + 2] = rows — the empty run every key without partner reads (unconditional loads in dd_count_kernel)
-__global__ void dd_table_kernel(const uint32_t *__restrict__ start, int64_t range, uint32_t rows, uint32_t *__restrict__ t) {
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i < range) t[i] = start[i];
-  else if (i < range + 3) t[i] = rows;
-}
-__global__ void dd_sort_keys_kernel(const uint64_t *__restrict__ keys, int64_t n, uint64_t kmin, uint64_t *__restrict__ out) {
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i < n) out[i] = keys[i] - kmin;
-}
-// the count pass over that table: match[r] = {run start, rows}, pair counts per row or per 64-row group (join_count_kernel's outputs)
-#ifndef DD_DBG
-#define DD_DBG 0
-#endif
-#ifndef DD_U_N
-#define DD_U_N 8
-#endif
-constexpr int DD_U = DD_U_N;
-struct __attribute__((aligned(4))) uint2_unaligned { uint32_t x, y; }; // (two adjacent 4-byte entries, one 8-byte load)
-// 64-row groups per wave: their keys, then their table entries, in flight together
-__global__ __launch_bounds__(BLOCK) void dd_count_kernel(const uint64_t *__restrict__ keys, const uint64_t *__restrict__ validity, int64_t n,
-                                                         uint64_t kmin, uint64_t range, const uint32_t *__restrict__ table, int outer_right,
-                                                         uint32_t *__restrict__ counts, uint2 *__restrict__ match, int grouped) {
-  const int lane = lane_id();
-  const int64_t wbase = (blockIdx.x * (int64_t)WAVES_PER_BLOCK + wave_id()) * (64 * DD_U);
-  if (wbase >= n) return;
-  uint64_t k[DD_U];
-#pragma unroll
-  for (int u = 0; u < DD_U; u++) k[u] = __builtin_nontemporal_load(keys + min(wbase + u * 64 + lane, n - 1));
-  unsigned long long m[DD_U];
-#pragma unroll
-  for (int u = 0; u < DD_U; u++) {
-    const int64_t r = min(wbase + u * 64 + lane, n - 1);
-    const bool is_null = validity && !((validity[r >> 6] >> (r & 63)) & 1); // (no NULL build key on this route: a NULL probe key has no partner)
-    const uint64_t d = k[u] - kmin;
-#if DD_DBG & 1 // (measurement: no table lookup)
-    m[u] = (!is_null && d < range) ? (d | (4ull << 32)) : 0ull;
-#else
-    // UNCONDITIONAL: a key without partner reads the empty entry behind the range — a load under a condition is a branch, and the
-    // eight lookups of a lane then wait for one another (0.73 ms per 1e8 rows; without any lookup 0.27)
-    // (4-byte entries, a run's length = the next start - its own: half the table of {start, rows} pairs, 1 MiB for 2.5e5 keys)
-    const uint2_unaligned se = *(const uint2_unaligned *)(table + ((!is_null && d < range) ? d : range + 1)); // {start, next start}
-    m[u] = (unsigned long long)se.x | ((unsigned long long)(se.y - se.x) << 32); // {run start | rows << 32}
-#endif
-  }
-#pragma unroll
-  for (int u = 0; u < DD_U; u++) {
-    const int64_t r = wbase + u * 64 + lane;
-    uint32_t c = 0;
-    if (r < n) {
-      c = (uint32_t)(m[u] >> 32);
-#if !(DD_DBG & 2) // (measurement: no match store)
-      __builtin_nontemporal_store(m[u], (unsigned long long *)(match + r));
-#endif
-      if (outer_right && c == 0) c = 1;
-      if (!grouped) counts[r] = c;
-    }
-    if (grouped) {
-      const uint32_t wsum = wave_sum_u32(c);
-      if (lane == 0 && wbase + u * 64 < n) counts[(wbase + u * 64) >> 6] = wsum;
-    }
-  }
-}
-// The same pass in the shape of join_probe_dense_allhit_packed_kernel (persistent waves, 512 CONSECUTIVE rows per wave and trip,
-// 16-byte key loads and match stores): probe keys without NULLs in a 16-byte aligned column.  The lookups and the two streams
-// share the CU's vector memory path; this shape is what got the all-hit probe from 0.69 to 0.52 ms per 1e8 rows (tools/ubench2.hip).
-__global__ __launch_bounds__(256) void dd_count_stream_kernel(const uint64_t *__restrict__ keys, int64_t n, uint64_t kmin, uint64_t range,
-                                                              const uint32_t *__restrict__ table, int outer_right,
-                                                              uint32_t *__restrict__ counts, uint2 *__restrict__ match, int grouped) {
-  const int lane = lane_id();
-  const int64_t nchunks = n / JAP_ROWS, gw = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)),
-                nw = (int64_t)gridDim.x * 4;
-  const uint32_t miss = (uint32_t)range + 1;
-  for (int64_t c = gw; c < nchunks; c += nw) {
-    const int64_t r0 = c * JAP_ROWS + 2 * lane;
-    u64x2_vec k[4];
-    uint2_unaligned se[8];
-#pragma unroll
-    for (int g = 0; g < 4; g++) k[g] = __builtin_nontemporal_load((const u64x2_vec *)(keys + r0 + g * 128));
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-      const uint64_t d0 = k[g].x - kmin, d1 = k[g].y - kmin;
-      se[2 * g] = *(const uint2_unaligned *)(table + (d0 < range ? (uint32_t)d0 : miss));
-      se[2 * g + 1] = *(const uint2_unaligned *)(table + (d1 < range ? (uint32_t)d1 : miss));
-    }
-#pragma unroll
-    for (int g = 0; g < 4; g++) { // rows r0 + 128 g, + 1: lanes 2 l, 2 l + 1 of the 128-row piece
-      const uint32_t c0 = se[2 * g].y - se[2 * g].x, c1 = se[2 * g + 1].y - se[2 * g + 1].x;
-      u64x2_vec mv;
-      mv.x = (unsigned long long)se[2 * g].x | ((unsigned long long)c0 << 32);
-      mv.y = (unsigned long long)se[2 * g + 1].x | ((unsigned long long)c1 << 32);
-      __builtin_nontemporal_store(mv, (u64x2_vec *)(match + r0 + g * 128));
-      const uint32_t e0 = (outer_right && c0 == 0) ? 1u : c0, e1 = (outer_right && c1 == 0) ? 1u : c1;
-      if (grouped) { // two 64-row groups per piece: lanes 0-31 hold the first, 32-63 the second
-        uint32_t v = e0 + e1;
-        for (int m = 16; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
-        if ((lane & 31) == 0) counts[((c * JAP_ROWS + g * 128) >> 6) + (lane >> 5)] = v;
-      } else {
-        *(uint2 *)(counts + r0 + g * 128) = make_uint2(e0, e1);
-      }
-    }
-  }
-  if (gw == nchunks % nw) // the rows behind the last whole chunk (< 512, whole 64-row groups first): the wave whose turn it would be
-    for (int64_t rb = nchunks * JAP_ROWS; rb < n; rb += 64) {
-      const int64_t r = rb + lane;
-      uint32_t cv = 0;
-      if (r < n) {
-        const uint64_t d = keys[r] - kmin;
-        const uint2_unaligned e = *(const uint2_unaligned *)(table + (d < range ? (uint32_t)d : miss));
-        const uint32_t c0 = e.y - e.x;
-        match[r] = make_uint2(e.x, c0);
-        cv = (outer_right && c0 == 0) ? 1u : c0;
-        if (!grouped) counts[r] = cv;
-      }
-      if (grouped) {
-        const uint32_t wsum = wave_sum_u32(cv);
-        if (lane == 0) counts[rb >> 6] = wsum;
-      }
-    }
-}
 static bool build_dense_dup(sqlrs_hash_join *j) {
   Ctx *ctx = j->ctx;
   if (!j->dup_range || !j->exact || !j->bkeys || j->bkeys_validity || j->nB <= 0 ||
@@ -613,11 +458,11 @@ static void build_hash_table(sqlrs_hash_join *j) {
   {
     ProfScope ps(ctx, "join_build");
     table_init_kernel<<<dim3((unsigned)ceil_div(nslots, 256)), dim3(256), 0, ctx->stream>>>(
-        (j->table ? j->table->as<Slot>() : nullptr), nslots);
+        slots_of(j), nslots);
     if (n)
       join_insert_kernel<<<dim3((unsigned)ceil_div(n, BLOCK)), dim3(BLOCK), 0, ctx->stream>>>(
           keys->as<uint64_t>(), validity ? validity->as<uint64_t>() : nullptr, n,
-          (j->table ? j->table->as<Slot>() : nullptr), j->mask, row_slot->as<uint32_t>(), dup->as<int>());
+          slots_of(j), j->mask, row_slot->as<uint32_t>(), dup->as<int>());
     SQ_HIP(hipGetLastError());
   }
   j->unique = ctx->fetch_value(dup->as<int>()) == 0;
@@ -627,11 +472,11 @@ static void build_hash_table(sqlrs_hash_join *j) {
     BufP counts = ctx->alloc(4 * (size_t)nslots), heads = ctx->alloc(4 * (size_t)nslots);
     BufP total = ctx->alloc(8);
     slot_counts_kernel<<<dim3((unsigned)ceil_div(nslots, 256)), dim3(256), 0, ctx->stream>>>(
-        (j->table ? j->table->as<Slot>() : nullptr), nslots, counts->as<uint32_t>());
+        slots_of(j), nslots, counts->as<uint32_t>());
     exclusive_scan_u32(ctx, counts->as<uint32_t>(), nslots, nullptr, heads->as<uint32_t>(),
                        total->as<uint64_t>());
     slot_heads_kernel<<<dim3((unsigned)ceil_div(nslots, 256)), dim3(256), 0, ctx->stream>>>(
-        (j->table ? j->table->as<Slot>() : nullptr), nslots, heads->as<uint32_t>());
+        slots_of(j), nslots, heads->as<uint32_t>());
     BufP k64 = ctx->alloc(8 * (size_t)n);
     j->rows_by_slot = ctx->alloc(4 * (size_t)n);
     u32_to_u64_kernel<<<dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream>>>(
@@ -665,179 +510,164 @@ DenseTable dense_table_of(const sqlrs_hash_join *j) { // (join_state.hpp)
   }
   return dt;
 }
-static Pairs probe_pairs(sqlrs_hash_join *j, const NKeys &pk) {
-  Ctx *ctx = j->ctx;
-  if (pk.exact != j->exact || (pk.exact && pk.dtype != j->key_dtype))
-    fail(SQLRS_ERR_INTERNAL, "join keys of different types on the two sides are not supported");
-  Pairs p;
-  int64_t n = pk.rows;
-  int outer_right = j->join_type == SQLRS_JOIN_RIGHT || j->join_type == SQLRS_JOIN_FULL;
-  // The first probe of a direct-address build whose verdict is still on the device: the optimistic all-hit kernel takes
-  // key range and uniqueness from the device-side words and ONE fetch brings back the build's verdict and the probe's —
-  // a host round trip less per join (C3: 8 MB of build keys cost 0.07 ms, a third of it that round trip).
-  if (j->dense_pending) {
-    const char *ah_e = hook("SQLRS_PROBE_ALLHIT");
-    if (!outer_right && !pk.validity && n >= (1 << 16) && n <= 0xffffffffll && j->pend_bits && !(ah_e && std::atoi(ah_e) == 0)) {
-      ProfScope ps(ctx, "join_probe_dense");
-      p.left = ctx->alloc(8 * (size_t)n);
-      p.right = ctx->alloc(4 * (size_t)n);
-      unsigned long long *stp = j->pend_st->as<unsigned long long>();
-      unsigned int *miss = (unsigned int *)(stp + DENSE_ST_WORDS);
-      DenseTable dt;
-      dt.heads = j->pend_dense->as<uint32_t>();
-      dt.packed = j->pend_packed->as<uint8_t>();
-      dt.bits = j->pend_bits;
-      dt.pmask = (1u << j->pend_bits) - 1;
-      dt.st = stp;
-      dt.st_max_range = j->pend_max_range;
-      dt.st_rows = (uint64_t)j->nB;
-      const int64_t every = std::max<int64_t>(1, n >> 14); // ~16 K sampled rows
-      join_probe_dense_sample_kernel<<<dim3((unsigned)ceil_div(ceil_div(n, every), 256)), dim3(256), 0, ctx->stream>>>(
-          pk.keys->as<uint64_t>(), n, every, dt, miss);
-      const unsigned pblocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n / JAP_ROWS, 4), JAP_GRID * (int64_t)ctx->num_cus));
-      if (((uintptr_t)pk.keys->p & 15) == 0)
-        join_probe_dense_allhit_packed_kernel<true><<<dim3(pblocks), dim3(256), 0, ctx->stream>>>(pk.keys->as<uint64_t>(), n, dt, p.left->as<uint64_t>(),
-                                                                                               p.right->as<uint32_t>(), miss);
-      else
-        join_probe_dense_allhit_packed_kernel<false><<<dim3(pblocks), dim3(256), 0, ctx->stream>>>(pk.keys->as<uint64_t>(), n, dt, p.left->as<uint64_t>(),
-                                                                                                p.right->as<uint32_t>(), miss);
-      SQ_HIP(hipGetLastError());
-      ctx->join_route[Ctx::JR_PROBE_PENDING]++;
-      uint64_t hw[DENSE_ST_WORDS + 1];
-      std::memcpy(hw, ctx->fetch(j->pend_st->p, 8 * (DENSE_ST_WORDS + 1)), sizeof(hw));
-      dense_resolve(j, hw);
-      ctx->join_route[(j->dense && (unsigned int)hw[DENSE_ST_WORDS] == 0) ? Ctx::JR_ALLHIT_KEPT : Ctx::JR_ALLHIT_REDONE]++;
-      if (j->dense && (unsigned int)hw[DENSE_ST_WORDS] == 0) { // a unique dense key set and every probe row found its partner
-        p.m = n;
-        p.right_identity = true;
-        return p;
-      }
-      if (j->dense) j->probe_miss_seen = true; // (later batches of this join go straight to the compacting kernel)
-      p = Pairs();
-    }
-  }
-  // a build side whose uniqueness came from its LDS bucket tables (lds_build_first) has no global table yet: it is built
-  // only when this batch cannot take the LDS route
-  LdsJoinMatch lm;
-  dense_resolve(j);
-  if (j->lds_first && !j->table_built && j->unique && !outer_right && !j->dense && n > 0) lm = lds_join_match(j, pk);
-  if (!lm.ok) hash_join_ensure_table(j);
-  if (n == 0) {
-    p.left = ctx->alloc(8);
-    p.right = ctx->alloc(8);
-    return p;
-  }
-  if (n > 0xffffffffll) fail(SQLRS_ERR_INTERNAL, "probe batch larger than 2^32 rows");
-  dim3 g((unsigned)ceil_div(n, BLOCK)), b(BLOCK);
-  // general keys, build side beyond an L2-resident table: LDS tables over a blocked partition (see lds_join_probe_kernel)
-  if (!lm.ok && j->unique && !outer_right && !j->dense) lm = lds_join_match(j, pk);
-  if (j->unique && !outer_right) { // one lookup per row, compaction with look-back
-    int64_t tiles = lm.ok ? lds_join_tiles(n) : ceil_div(n, j->dense ? JD_TILE : JP_TILE);
-    p.left = ctx->alloc(8 * (size_t)n);
-    p.right = ctx->alloc(4 * (size_t)n);
-    // optimistic all-hit attempt of the direct-address probe (join_probe_dense_allhit_kernel); its miss flag is a word of its
-    // own (a zeroed slab: no memset) and is NOT cleared by a look-back rerun.  SQLRS_PROBE_ALLHIT=0 (read per call): never.
-    // The look-back descriptors are allocated (and cleared: a memset) only when the compacting kernel runs.
-    unsigned int *miss = nullptr;
-    BufP miss_buf;
-    {
-      const char *ah_e = hook("SQLRS_PROBE_ALLHIT");
-      if (j->dense && !lm.ok && !pk.validity && n >= (1 << 16) && !j->probe_miss_seen && !(ah_e && std::atoi(ah_e) == 0)) {
-        miss_buf = ctx->alloc_zero(8);
-        miss = miss_buf->as<unsigned int>();
-        ProfScope ps(ctx, "join_probe_dense");
-        DenseTable dt = dense_table_of(j);
-        const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(n, 256 * JA_ILP), 16 * (int64_t)ctx->num_cus);
-        const int64_t every = std::max<int64_t>(1, n >> 14); // ~16 K sampled rows
-        join_probe_dense_sample_kernel<<<dim3((unsigned)ceil_div(ceil_div(n, every), 256)), dim3(256), 0, ctx->stream>>>(
-            pk.keys->as<uint64_t>(), n, every, dt, miss);
-        if (dt.packed) { // wave-contiguous chunks over the bit-packed table
-          const unsigned pblocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n / JAP_ROWS, 4), JAP_GRID * (int64_t)ctx->num_cus));
-          if (((uintptr_t)pk.keys->p & 15) == 0)
-            join_probe_dense_allhit_packed_kernel<true><<<dim3(pblocks), dim3(256), 0, ctx->stream>>>(pk.keys->as<uint64_t>(), n, dt, p.left->as<uint64_t>(),
-                                                                                                   p.right->as<uint32_t>(), miss);
-          else
-            join_probe_dense_allhit_packed_kernel<false><<<dim3(pblocks), dim3(256), 0, ctx->stream>>>(pk.keys->as<uint64_t>(), n, dt, p.left->as<uint64_t>(),
-                                                                                                    p.right->as<uint32_t>(), miss);
-        } else
-          join_probe_dense_allhit_kernel<<<dim3(blocks), dim3(256), 0, ctx->stream>>>(pk.keys->as<uint64_t>(), n, dt, p.left->as<uint64_t>(),
-                                                                                           p.right->as<uint32_t>(), miss);
-        SQ_HIP(hipGetLastError());
-        const bool all_hit = ctx->fetch_value(miss) == 0;
-        ctx->join_route[all_hit ? Ctx::JR_ALLHIT_KEPT : Ctx::JR_ALLHIT_REDONE]++;
-        if (all_hit) { // every pair is in place
-          p.m = n;
-          p.right_identity = true;
-          return p;
-        }
-        j->probe_miss_seen = true; // (later batches of this join go straight to the compacting kernel)
-      }
-    }
-    BufP desc = ctx->alloc_zero(8 * (size_t)tiles + 24);
-    unsigned *ticket = (unsigned *)(desc->as<uint64_t>() + tiles);
-    uint64_t *tot = desc->as<uint64_t>() + tiles + 1;
-    if (!lm.ok) ctx->join_route[j->dense ? Ctx::JR_COMPACT_DENSE : Ctx::JR_COMPACT_SLOTS]++;
-    for (int use_ticket = lookback_start_mode(ctx), attempt = 0; use_ticket < 2; use_ticket++, attempt++) {
-      if (attempt) SQ_HIP(hipMemsetAsync(desc->p, 0, 8 * (size_t)tiles + 16, ctx->stream)); // rerun after a timeout
-      {
-        ProfScope ps(ctx, lm.ok ? "join_match_compact" : (j->dense ? "join_probe_dense" : "join_probe_unique"));
-        dim3 gt((unsigned)tiles);
-        DenseTable dt = dense_table_of(j);
-        if (lm.ok) {
-          lds_join_restore(ctx, lm, n, p.left->as<uint64_t>(), p.right->as<uint32_t>(), desc->as<uint64_t>(), ticket, tot, use_ticket);
-        } else if (j->dense && pk.validity)
-          join_probe_dense_kernel<true><<<gt, dim3(JD_BLOCK), 0, ctx->stream>>>(
-              pk.keys->as<uint64_t>(), pk.validity, n, tiles, dt, p.left->as<uint64_t>(), p.right->as<uint32_t>(),
-              desc->as<uint64_t>(), ticket, tot, use_ticket);
-        else if (j->dense)
-          join_probe_dense_kernel<false><<<gt, dim3(JD_BLOCK), 0, ctx->stream>>>(
-              pk.keys->as<uint64_t>(), pk.validity, n, tiles, dt, p.left->as<uint64_t>(), p.right->as<uint32_t>(),
-              desc->as<uint64_t>(), ticket, tot, use_ticket, miss);
-        else
-          join_probe_unique_kernel<false><<<gt, b, 0, ctx->stream>>>(
-              pk.keys->as<uint64_t>(), pk.validity, n, tiles, (j->table ? j->table->as<Slot>() : nullptr), j->mask, dt,
-              p.left->as<uint64_t>(), p.right->as<uint32_t>(), desc->as<uint64_t>(), ticket, tot, use_ticket);
-        SQ_HIP(hipGetLastError());
-      }
-      const uint64_t *h = (const uint64_t *)ctx->fetch(ticket, 16); // {ticket|timeout, total}
-      p.m = (int64_t)h[1];
-      if (use_ticket || (h[0] >> 32) == 0) break;
-      lookback_timed_out(ctx);
-    }
-    // unique build keys, pairs in probe-row order: as many pairs as probe rows = every row matched once = pair i is (.., i)
-    p.right_identity = p.m == n;
-    return p;
-  }
-  // duplicate build keys, and Right / Full joins over general keys: matched on the LDS tables too, un-permuted into the
-  // {run, pairs} the fill pass expands (lds_join_unpermute_kernel)
-  LdsJoinMatch lmg;
-  if (!j->dense && !j->dd_table && (!j->unique || outer_right)) lmg = lds_join_match(j, pk, !j->unique);
-  if (j->unique && outer_right && !lmg.ok) { // exactly one pair per probe row
-    p.m = n;
-    p.right_identity = true; // (pair i = (build row | NULL, probe row i))
-    p.left = ctx->alloc(8 * (size_t)n);
-    p.right = ctx->alloc(4 * (size_t)n);
-    p.left_validity = ctx->alloc(bitmap_bytes(n));
-    ProfScope ps(ctx, "join_probe_unique");
-    ctx->join_route[Ctx::JR_UNIQUE_OUTER]++;
-    int64_t n64 = (int64_t)round_up((size_t)n, 64);
-    DenseTable dt = dense_table_of(j);
-    if (j->dense)
-      join_probe_unique_outer_kernel<true><<<dim3((unsigned)ceil_div(n64, BLOCK)), b, 0, ctx->stream>>>(
-          pk.keys->as<uint64_t>(), pk.validity, n, (j->table ? j->table->as<Slot>() : nullptr), j->mask, dt, p.left->as<uint64_t>(),
-          p.right->as<uint32_t>(), p.left_validity->as<uint64_t>());
+
+// ---- probe: one function per route, probe_pairs chooses -------------------------------------------------------------------
+// The optimistic all-hit attempt of the direct-address probe.  SQLRS_PROBE_ALLHIT=0 (read per call): never.
+static bool allhit_wanted(const NKeys &pk) {
+  return !hook_is_zero(hook("SQLRS_PROBE_ALLHIT")) && !pk.validity && pk.rows >= (1 << 16); // A/B hook, read per call
+}
+// its launches: a sample of rows first (a batch with misses raises `miss` early), then every row
+static void launch_allhit(Ctx *ctx, const NKeys &pk, int64_t n, const DenseTable &dt, uint64_t *left, uint32_t *right, unsigned int *miss) {
+  const uint64_t *keys = pk.keys->as<uint64_t>();
+  const int64_t every = std::max<int64_t>(1, n >> 14); // ~16 K sampled rows
+  join_probe_dense_sample_kernel<<<dim3((unsigned)ceil_div(ceil_div(n, every), 256)), dim3(256), 0, ctx->stream>>>(keys, n, every, dt, miss);
+  if (dt.packed) { // wave-contiguous chunks over the bit-packed table
+    const unsigned pblocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n / JAP_ROWS, 4), JAP_GRID * (int64_t)ctx->num_cus));
+    if (((uintptr_t)pk.keys->p & 15) == 0)
+      join_probe_dense_allhit_packed_kernel<true><<<dim3(pblocks), dim3(256), 0, ctx->stream>>>(keys, n, dt, left, right, miss);
     else
-      join_probe_unique_outer_kernel<false><<<dim3((unsigned)ceil_div(n64, BLOCK)), b, 0, ctx->stream>>>(
-          pk.keys->as<uint64_t>(), pk.validity, n, (j->table ? j->table->as<Slot>() : nullptr), j->mask, dt, p.left->as<uint64_t>(),
-          p.right->as<uint32_t>(), p.left_validity->as<uint64_t>());
-    SQ_HIP(hipGetLastError());
-    return p;
+      join_probe_dense_allhit_packed_kernel<false><<<dim3(pblocks), dim3(256), 0, ctx->stream>>>(keys, n, dt, left, right, miss);
+  } else {
+    const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(n, 256 * JA_ILP), 16 * (int64_t)ctx->num_cus);
+    join_probe_dense_allhit_kernel<<<dim3(blocks), dim3(256), 0, ctx->stream>>>(keys, n, dt, left, right, miss);
   }
+  SQ_HIP(hipGetLastError());
+}
+// its outcome: kept, or redone by the compacting kernel, as later batches of this join then are at once
+static bool allhit_kept(sqlrs_hash_join *j, bool kept) {
+  j->ctx->join_route[kept ? Ctx::JR_ALLHIT_KEPT : Ctx::JR_ALLHIT_REDONE]++;
+  if (!kept && j->dense) j->probe_miss_seen = true;
+  return kept;
+}
+// The first probe of a direct-address build whose verdict is still on the device: the all-hit kernel takes key range and
+// uniqueness from the device-side words and ONE fetch brings back the build's verdict and the probe's — a host round trip
+// less per join (C3: 8 MB of build keys cost 0.07 ms, a third of it that round trip).  true: `out` holds the pairs — a unique
+// dense key set and every probe row found its partner; false: the build is resolved, the batch is still to be probed.
+static bool probe_allhit_pending(sqlrs_hash_join *j, const NKeys &pk, Pairs *out) {
+  Ctx *ctx = j->ctx;
+  const int64_t n = pk.rows;
+  ProfScope ps(ctx, "join_probe_dense");
+  Pairs p;
+  p.left = ctx->alloc(8 * (size_t)n);
+  p.right = ctx->alloc(4 * (size_t)n);
+  unsigned long long *stp = j->pend_st->as<unsigned long long>();
+  unsigned int *miss = (unsigned int *)(stp + DENSE_ST_WORDS);
+  DenseTable dt;
+  dt.heads = j->pend_dense->as<uint32_t>();
+  dt.packed = j->pend_packed->as<uint8_t>();
+  dt.bits = j->pend_bits;
+  dt.pmask = (1u << j->pend_bits) - 1;
+  dt.st = stp;
+  dt.st_max_range = j->pend_max_range;
+  dt.st_rows = (uint64_t)j->nB;
+  launch_allhit(ctx, pk, n, dt, p.left->as<uint64_t>(), p.right->as<uint32_t>(), miss);
+  ctx->join_route[Ctx::JR_PROBE_PENDING]++;
+  uint64_t hw[DENSE_ST_WORDS + 1];
+  std::memcpy(hw, ctx->fetch(j->pend_st->p, 8 * (DENSE_ST_WORDS + 1)), sizeof(hw));
+  dense_resolve(j, hw);
+  if (!allhit_kept(j, j->dense && (unsigned int)hw[DENSE_ST_WORDS] == 0)) return false;
+  p.m = n;
+  p.right_identity = true;
+  *out = p;
+  return true;
+}
+// unique build keys, Inner / Left: hits compacted with look-back over the LDS route's match (`lm`), the dense or the slot table
+static Pairs probe_unique_inner(sqlrs_hash_join *j, const NKeys &pk, const LdsJoinMatch &lm) {
+  Ctx *ctx = j->ctx;
+  const int64_t n = pk.rows;
+  Pairs p;
+  int64_t tiles = lm.ok ? lds_join_tiles(n) : ceil_div(n, j->dense ? JD_TILE : JP_TILE);
+  p.left = ctx->alloc(8 * (size_t)n);
+  p.right = ctx->alloc(4 * (size_t)n);
+  // the all-hit attempt first (join_probe_dense_allhit_kernel); its miss flag is a word of its own (a zeroed slab: no memset)
+  // and is NOT cleared by a look-back rerun.  The look-back descriptors are allocated (and cleared: a memset) only when the
+  // compacting kernel runs.
+  unsigned int *miss = nullptr;
+  BufP miss_buf;
+  if (allhit_wanted(pk) && j->dense && !lm.ok && !j->probe_miss_seen) {
+    miss_buf = ctx->alloc_zero(8);
+    miss = miss_buf->as<unsigned int>();
+    ProfScope ps(ctx, "join_probe_dense");
+    launch_allhit(ctx, pk, n, dense_table_of(j), p.left->as<uint64_t>(), p.right->as<uint32_t>(), miss);
+    if (allhit_kept(j, ctx->fetch_value(miss) == 0)) {
+      p.m = n;
+      p.right_identity = true;
+      return p;
+    }
+  }
+  BufP desc = ctx->alloc_zero(8 * (size_t)tiles + 24);
+  unsigned *ticket = (unsigned *)(desc->as<uint64_t>() + tiles);
+  uint64_t *tot = desc->as<uint64_t>() + tiles + 1;
+  if (!lm.ok) ctx->join_route[j->dense ? Ctx::JR_COMPACT_DENSE : Ctx::JR_COMPACT_SLOTS]++;
+  for (int use_ticket = lookback_start_mode(ctx), attempt = 0; use_ticket < 2; use_ticket++, attempt++) {
+    if (attempt) SQ_HIP(hipMemsetAsync(desc->p, 0, 8 * (size_t)tiles + 16, ctx->stream)); // rerun after a timeout
+    {
+      ProfScope ps(ctx, lm.ok ? "join_match_compact" : (j->dense ? "join_probe_dense" : "join_probe_unique"));
+      dim3 gt((unsigned)tiles);
+      DenseTable dt = dense_table_of(j);
+      if (lm.ok) {
+        lds_join_restore(ctx, lm, n, p.left->as<uint64_t>(), p.right->as<uint32_t>(), desc->as<uint64_t>(), ticket, tot, use_ticket);
+      } else if (j->dense && pk.validity)
+        join_probe_dense_kernel<true><<<gt, dim3(JD_BLOCK), 0, ctx->stream>>>(
+            pk.keys->as<uint64_t>(), pk.validity, n, tiles, dt, p.left->as<uint64_t>(), p.right->as<uint32_t>(),
+            desc->as<uint64_t>(), ticket, tot, use_ticket);
+      else if (j->dense)
+        join_probe_dense_kernel<false><<<gt, dim3(JD_BLOCK), 0, ctx->stream>>>(
+            pk.keys->as<uint64_t>(), pk.validity, n, tiles, dt, p.left->as<uint64_t>(), p.right->as<uint32_t>(),
+            desc->as<uint64_t>(), ticket, tot, use_ticket, miss);
+      else
+        join_probe_unique_kernel<false><<<gt, dim3(BLOCK), 0, ctx->stream>>>(
+            pk.keys->as<uint64_t>(), pk.validity, n, tiles, slots_of(j), j->mask, dt,
+            p.left->as<uint64_t>(), p.right->as<uint32_t>(), desc->as<uint64_t>(), ticket, tot, use_ticket);
+      SQ_HIP(hipGetLastError());
+    }
+    const uint64_t *h = (const uint64_t *)ctx->fetch(ticket, 16); // {ticket|timeout, total}
+    p.m = (int64_t)h[1];
+    if (use_ticket || (h[0] >> 32) == 0) break;
+    lookback_timed_out(ctx);
+  }
+  // unique build keys, pairs in probe-row order: as many pairs as probe rows = every row matched once = pair i is (.., i)
+  p.right_identity = p.m == n;
+  return p;
+}
+// unique build keys, Right / Full: exactly one pair per probe row, pair i = (build row | NULL, probe row i)
+static Pairs probe_unique_outer(sqlrs_hash_join *j, const NKeys &pk) {
+  Ctx *ctx = j->ctx;
+  const int64_t n = pk.rows;
+  Pairs p;
+  p.m = n;
+  p.right_identity = true;
+  p.left = ctx->alloc(8 * (size_t)n);
+  p.right = ctx->alloc(4 * (size_t)n);
+  p.left_validity = ctx->alloc(bitmap_bytes(n));
+  ProfScope ps(ctx, "join_probe_unique");
+  ctx->join_route[Ctx::JR_UNIQUE_OUTER]++;
+  int64_t n64 = (int64_t)round_up((size_t)n, 64);
+  DenseTable dt = dense_table_of(j);
+  if (j->dense)
+    join_probe_unique_outer_kernel<true><<<dim3((unsigned)ceil_div(n64, BLOCK)), dim3(BLOCK), 0, ctx->stream>>>(
+        pk.keys->as<uint64_t>(), pk.validity, n, slots_of(j), j->mask, dt, p.left->as<uint64_t>(),
+        p.right->as<uint32_t>(), p.left_validity->as<uint64_t>());
+  else
+    join_probe_unique_outer_kernel<false><<<dim3((unsigned)ceil_div(n64, BLOCK)), dim3(BLOCK), 0, ctx->stream>>>(
+        pk.keys->as<uint64_t>(), pk.validity, n, slots_of(j), j->mask, dt, p.left->as<uint64_t>(),
+        p.right->as<uint32_t>(), p.left_validity->as<uint64_t>());
+  SQ_HIP(hipGetLastError());
+  return p;
+}
+// duplicate build keys, and Right / Full joins over general keys: count matches per probe row -> exclusive scan -> fill.  The
+// count comes from the LDS route's match (`lmg`, un-permuted into {run, pairs}), from dd_table, or from the slot table.
+static Pairs probe_counted(sqlrs_hash_join *j, const NKeys &pk, const LdsJoinMatch &lmg) {
+  Ctx *ctx = j->ctx;
+  const int64_t n = pk.rows;
+  const int outer_right = is_outer_right(j);
+  Pairs p;
+  dim3 g((unsigned)ceil_div(n, BLOCK)), b(BLOCK);
   // The fill pass scans the pair counts of its 64 probe rows itself, so only one sum per 64-row group is scanned globally
   // (round 6: per-row counts + offsets were 0.4 + 0.8 GB written and 1.2 GB read for 1e8 probe rows, 0.45 ms of scan).  A build
   // side of >= 2^26 rows — 64 runs of that length overflow a 32-bit sum — keeps per-row counts.
-  const char *gr_e = hook("SQLRS_JOIN_GROUPED"); // test hook, read per call: 0 = per-row counts whatever the build side's size
-  const int grouped = (j->nB < (1ll << 26) && !(gr_e && std::atoi(gr_e) == 0)) ? 1 : 0;
+  const bool per_row = hook_is_zero(hook("SQLRS_JOIN_GROUPED")); // test hook, read per call: 0 = per-row counts whatever the build side's size
+  const int grouped = (j->nB < (1ll << 26) && !per_row) ? 1 : 0;
   ctx->join_route[grouped ? Ctx::JR_COUNTS_GROUPED : Ctx::JR_COUNTS_PER_ROW]++;
   const int64_t nscan = grouped ? ceil_div(n, 64) : n;
   BufP counts = ctx->alloc(4 * (size_t)nscan), offsets = ctx->alloc(8 * (size_t)nscan), total = ctx->alloc(8);
@@ -859,8 +689,7 @@ static Pairs probe_pairs(sqlrs_hash_join *j, const NKeys &pk) {
     SQ_HIP(hipGetLastError());
   } else {
     ProfScope ps(ctx, "join_probe_count");
-    join_count_kernel<<<g, b, 0, ctx->stream>>>(pk.keys->as<uint64_t>(), pk.validity, n,
-                                                (j->table ? j->table->as<Slot>() : nullptr), j->mask, outer_right,
+    join_count_kernel<<<g, b, 0, ctx->stream>>>(pk.keys->as<uint64_t>(), pk.validity, n, slots_of(j), j->mask, outer_right,
                                                 counts->as<uint32_t>(), match->as<uint2>(), grouped);
     SQ_HIP(hipGetLastError());
   }
@@ -874,7 +703,7 @@ static Pairs probe_pairs(sqlrs_hash_join *j, const NKeys &pk) {
   if (outer_right) lvb = ctx->alloc((size_t)m1);
   if (p.m) {
     ProfScope ps(ctx, "join_probe_fill");
-    join_fill_expand_kernel<<<dim3((unsigned)ceil_div(n, BLOCK)), b, 0, ctx->stream>>>(
+    join_fill_expand_kernel<<<g, b, 0, ctx->stream>>>(
         match->as<uint2>(), n, j->unique ? 1 : 0, outer_right, j->rows_by_slot ? j->rows_by_slot->as<uint32_t>() : nullptr,
         offsets->as<uint64_t>(), p.left->as<uint64_t>(), p.right->as<uint32_t>(), lvb ? lvb->as<uint8_t>() : nullptr, grouped);
     SQ_HIP(hipGetLastError());
@@ -888,6 +717,36 @@ static Pairs probe_pairs(sqlrs_hash_join *j, const NKeys &pk) {
   }
   return p;
 }
+// which route a probe batch takes (tests/test_gpu_join_edges.py, Plan.probe, restates this order of conditions)
+static Pairs probe_pairs(sqlrs_hash_join *j, const NKeys &pk) {
+  Ctx *ctx = j->ctx;
+  if (pk.exact != j->exact || (pk.exact && pk.dtype != j->key_dtype))
+    fail(SQLRS_ERR_INTERNAL, "join keys of different types on the two sides are not supported");
+  Pairs p;
+  const int64_t n = pk.rows;
+  const bool outer_right = is_outer_right(j);
+  if (j->dense_pending && allhit_wanted(pk) && !outer_right && n <= 0xffffffffll && j->pend_bits)
+    if (probe_allhit_pending(j, pk, &p)) return p; // (false: the build is resolved, the batch still to be probed)
+  // (a build side whose uniqueness came from lds_build_first has no global table yet: built only when this batch needs it)
+  LdsJoinMatch lm;
+  dense_resolve(j);
+  if (j->lds_first && !j->table_built && j->unique && !outer_right && !j->dense && n > 0) lm = lds_join_match(j, pk);
+  if (!lm.ok) hash_join_ensure_table(j);
+  if (n == 0) {
+    p.left = ctx->alloc(8);
+    p.right = ctx->alloc(8);
+    return p;
+  }
+  if (n > 0xffffffffll) fail(SQLRS_ERR_INTERNAL, "probe batch larger than 2^32 rows");
+  // general keys, build side beyond an L2-resident table: LDS tables over a blocked partition (see lds_join_probe_kernel)
+  if (!lm.ok && j->unique && !outer_right && !j->dense) lm = lds_join_match(j, pk);
+  if (j->unique && !outer_right) return probe_unique_inner(j, pk, lm);
+  // duplicate build keys, and Right / Full joins over general keys: matched on the LDS tables too
+  LdsJoinMatch lmg;
+  if (!j->dense && !j->dd_table && (!j->unique || outer_right)) lmg = lds_join_match(j, pk, !j->unique);
+  if (j->unique && outer_right && !lmg.ok) return probe_unique_outer(j, pk);
+  return probe_counted(j, pk, lmg);
+}
 
 static DBatch gather_pairs(sqlrs_hash_join *j, const DBatch &right, const Pairs &p) {
   Ctx *ctx = j->ctx;
@@ -899,8 +758,7 @@ static DBatch gather_pairs(sqlrs_hash_join *j, const DBatch &right, const Pairs 
   // Inner/Left the gathered build key column is the gathered probe key column: the random
   // gather over the build side is skipped.
   int lkey_col = -1, rkey_col = -1;
-  bool outer_right = j->join_type == SQLRS_JOIN_RIGHT || j->join_type == SQLRS_JOIN_FULL;
-  if (!outer_right && j->exact && j->lkeys.size() == 1 && j->lkeys[0].nodes.size() == 1 &&
+  if (!is_outer_right(j) && j->exact && j->lkeys.size() == 1 && j->lkeys[0].nodes.size() == 1 &&
       j->rkeys[0].nodes.size() == 1 && j->lkeys[0].nodes[0].op == SQLRS_EXPR_INPUT_REF &&
       j->rkeys[0].nodes[0].op == SQLRS_EXPR_INPUT_REF) {
     lkey_col = j->lkeys[0].nodes[0].index;
@@ -935,22 +793,9 @@ static void apply_filter(sqlrs_hash_join *j, const DBatch &right, Pairs &p) {
   mask.length = inter.rows;
   Selection sel = selection_from_mask(ctx, mask);
   DCol lcol, rcol;
-  lcol.dtype = SQLRS_UINT64;
-  lcol.length = p.m;
-  lcol.values = p.left->p;
-  lcol.own_values = p.left;
-  if (p.left_validity) {
-    lcol.validity = p.left_validity->as<uint64_t>();
-    lcol.own_validity = p.left_validity;
-    lcol.null_count = -1;
-  }
-  rcol.dtype = SQLRS_UINT32;
-  rcol.length = p.m;
-  rcol.values = p.right->p;
-  rcol.own_values = p.right;
+  pairs_as_columns(p, &lcol, &rcol);
   DCol lf = compact_column(ctx, lcol, sel), rf = compact_column(ctx, rcol, sel);
-  bool outer_right = j->join_type == SQLRS_JOIN_RIGHT || j->join_type == SQLRS_JOIN_FULL;
-  if (!outer_right) {
+  if (!is_outer_right(j)) {
     p.m = sel.count;
     p.left = lf.own_values;
     p.right = rf.own_values;
@@ -982,10 +827,6 @@ static void apply_filter(sqlrs_hash_join *j, const DBatch &right, Pairs &p) {
   if (!p.left_validity && unv.count == 0 && lf.own_validity) p.left_validity = lf.own_validity;
 }
 
-__global__ void dup_mult_kernel(const uint64_t *__restrict__ keys, int64_t n, uint64_t kmin, uint32_t *__restrict__ mult) {
-  const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (r < n) atomicAdd(&mult[keys[r] - kmin], 1u);
-}
 const uint32_t *hash_join_dup_mult(sqlrs_hash_join *j) {
   dense_resolve(j);
   if (!j->dup_range || !j->bkeys || j->bkeys_validity) return nullptr;
@@ -1159,7 +1000,7 @@ static int hash_join_build_push_device(sqlrs_hash_join_t *j, const sqlrs_batch_t
       if (i < 0 || (size_t)i >= b.cols.size()) fail(SQLRS_ERR_INTERNAL, "input ref out of range");
       return b.cols[(size_t)i];
     };
-    // (the evaluated key columns are kept only for the opt-in composite key, build_table: 8 B x rows x keys of device memory
+    // (the evaluated key columns are kept only for the opt-in composite key, concat_build_keys: 8 B x rows x keys of device memory
     //  otherwise held until build_finish for nothing)
     const char *ck_e = std::getenv("SQLRS_JOIN_COMPOSITE");
     if (j->lkeys.size() >= 2 && j->lkeys.size() <= 4 && !j->lazy_table && ck_e && std::atoi(ck_e) == 1) {
@@ -1215,27 +1056,6 @@ int sqlrs_hash_join_probe_push(sqlrs_hash_join_t *j, const sqlrs_batch_t *right,
     *out = emit_batch(j->ctx, std::move(r), out_mem);
   });
 }
-
-} // extern "C"
-
-namespace sq {
-// cut[i] = pairs whose probe row (right[], ascending: pairs are probe-row major) lies before bounds[i]
-__global__ void pairs_before_kernel(const uint32_t *__restrict__ right, int64_t m, const int64_t *__restrict__ bounds, int64_t n,
-                                    int64_t *__restrict__ cut) {
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int64_t b = bounds[i];
-  int64_t lo = 0, hi = m; // first pair with right >= b
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if ((int64_t)right[mid] < b) lo = mid + 1;
-    else hi = mid;
-  }
-  cut[i] = lo;
-}
-} // namespace sq
-
-extern "C" {
 
 // n probe batches in one call: out[i] is what sqlrs_hash_join_probe_push(right[i]) returns [ref: hash_join.rs:207-292: one
 // joined batch per probe batch] — for the reference's batch shape, 1024-row HOST batches (storage/csv.rs:105), where one
@@ -1332,19 +1152,7 @@ int sqlrs_hash_join_probe_indices(sqlrs_hash_join_t *j, const sqlrs_batch_t *rig
     DBatch b;
     b.rows = p.m;
     DCol l, r;
-    l.dtype = SQLRS_UINT64;
-    l.length = p.m;
-    l.values = p.left->p;
-    l.own_values = p.left;
-    if (p.left_validity) {
-      l.validity = p.left_validity->as<uint64_t>();
-      l.own_validity = p.left_validity;
-      l.null_count = -1;
-    }
-    r.dtype = SQLRS_UINT32;
-    r.length = p.m;
-    r.values = p.right->p;
-    r.own_values = p.right;
+    pairs_as_columns(p, &l, &r);
     b.cols.push_back(std::move(l));
     b.cols.push_back(std::move(r));
     *out = emit_batch(j->ctx, std::move(b), out_mem);

@@ -1,7 +1,7 @@
 // join_probe_kernels.hpp — the device side of join.hip (round 6: moved out of the operator file, which keeps the host logic; one
 // translation unit as before).  The open-addressing table (insert / count / fill), the direct-address table (build without a host
-// round trip, the bit-packed copy, the all-hit and the compacting probe kernels), the existence bitmap of a key-only build side and
-// the outer-join marks.  hash_join.rs:146-323; what each kernel replaces is cited at the kernel.
+// round trip, the bit-packed copy, the all-hit and the compacting probe kernels), the existence bitmap of a key-only build side,
+// the outer-join marks, the composite key of several key columns, and the runs by key of duplicate keys over a dense range.  hash_join.rs:146-323; what each kernel replaces is cited at the kernel.
 #pragma once
 #include "common.hpp"
 #include "device_utils.hpp"
@@ -892,6 +892,181 @@ __global__ void mark_bits_kernel(const I *__restrict__ idx, const uint64_t *__re
   const unsigned long long bit = 1ull << (x & 63);
   if (__hip_atomic_load(&bits[x >> 6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) return;
   atomicOr(&bits[x >> 6], bit);
+}
+
+// ---- several integer key columns as ONE exact key (sqlrs_hash_join::Composite; join.hip, composite_build_keys) ----------
+struct CompJoinKeys {
+  const void *vals[4];
+  const uint64_t *valid[4];
+  int64_t min[4];
+  uint64_t range[4], stride[4];
+  int is32[4];
+  int nk; // < 0: every row gets the no-match key (key column types differ between the sides)
+};
+constexpr uint64_t COMP_NO_MATCH = ~0ull; // (composites are < 2^62)
+__device__ __forceinline__ int64_t comp_value(const CompJoinKeys &ck, int c, int64_t i) {
+  return ck.is32[c] ? (int64_t)((const int32_t *)ck.vals[c])[i] : ((const int64_t *)ck.vals[c])[i];
+}
+__global__ __launch_bounds__(256) void comp_join_minmax_kernel(const void *__restrict__ vals, int is32, int64_t n, long long *mm) {
+  long long lo = INT64_MAX, hi = INT64_MIN;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const long long v = is32 ? (long long)((const int32_t *)vals)[i] : ((const long long *)vals)[i];
+    lo = min(lo, v);
+    hi = max(hi, v);
+  }
+  for (int m = 32; m >= 1; m >>= 1) {
+    lo = min(lo, (long long)shfl_xor_u64((uint64_t)lo, m));
+    hi = max(hi, (long long)shfl_xor_u64((uint64_t)hi, m));
+  }
+  if (lane_id() == 0) {
+    atomicMin(mm, lo);
+    atomicMax(mm + 1, hi);
+  }
+}
+__global__ __launch_bounds__(256) void comp_join_keys_kernel(CompJoinKeys ck, int64_t n, uint64_t *__restrict__ out) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint64_t key = 0;
+  bool ok = ck.nk > 0;
+  for (int c = 0; c < ck.nk && ok; c++) {
+    if (ck.valid[c] && !((ck.valid[c][i >> 6] >> (i & 63)) & 1ull)) ok = false;
+    else {
+      const uint64_t d = (uint64_t)comp_value(ck, c, i) - (uint64_t)ck.min[c]; // (wraps to a huge value below the minimum)
+      if (d >= ck.range[c]) ok = false;
+      else key += d * ck.stride[c];
+    }
+  }
+  out[i] = ok ? key : COMP_NO_MATCH;
+}
+
+// ---- duplicate build keys over a dense range (join.hip, build_dense_dup) -------------------------------------------------
+// the run starts with three entries behind the range: start[range] = rows (the end of the last run), start[range + 1] =
+// start[range + 2] = rows — the empty run every key without partner reads (unconditional loads in dd_count_kernel)
+__global__ void dd_table_kernel(const uint32_t *__restrict__ start, int64_t range, uint32_t rows, uint32_t *__restrict__ t) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i < range) t[i] = start[i];
+  else if (i < range + 3) t[i] = rows;
+}
+__global__ void dd_sort_keys_kernel(const uint64_t *__restrict__ keys, int64_t n, uint64_t kmin, uint64_t *__restrict__ out) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i < n) out[i] = keys[i] - kmin;
+}
+// the count pass over that table: match[r] = {run start, rows}, pair counts per row or per 64-row group (join_count_kernel's outputs)
+constexpr int DD_U = 8;
+struct __attribute__((aligned(4))) uint2_unaligned { uint32_t x, y; }; // (two adjacent 4-byte entries, one 8-byte load)
+// 64-row groups per wave: their keys, then their table entries, in flight together
+__global__ __launch_bounds__(BLOCK) void dd_count_kernel(const uint64_t *__restrict__ keys, const uint64_t *__restrict__ validity, int64_t n,
+                                                         uint64_t kmin, uint64_t range, const uint32_t *__restrict__ table, int outer_right,
+                                                         uint32_t *__restrict__ counts, uint2 *__restrict__ match, int grouped) {
+  const int lane = lane_id();
+  const int64_t wbase = (blockIdx.x * (int64_t)WAVES_PER_BLOCK + wave_id()) * (64 * DD_U);
+  if (wbase >= n) return;
+  uint64_t k[DD_U];
+#pragma unroll
+  for (int u = 0; u < DD_U; u++) k[u] = __builtin_nontemporal_load(keys + min(wbase + u * 64 + lane, n - 1));
+  unsigned long long m[DD_U];
+#pragma unroll
+  for (int u = 0; u < DD_U; u++) {
+    const int64_t r = min(wbase + u * 64 + lane, n - 1);
+    const bool is_null = validity && !((validity[r >> 6] >> (r & 63)) & 1); // (no NULL build key on this route: a NULL probe key has no partner)
+    const uint64_t d = k[u] - kmin;
+    // UNCONDITIONAL: a key without partner reads the empty entry behind the range — a load under a condition is a branch, and the
+    // eight lookups of a lane then wait for one another (0.73 ms per 1e8 rows; without any lookup 0.27)
+    // (4-byte entries, a run's length = the next start - its own: half the table of {start, rows} pairs, 1 MiB for 2.5e5 keys)
+    const uint2_unaligned se = *(const uint2_unaligned *)(table + ((!is_null && d < range) ? d : range + 1)); // {start, next start}
+    m[u] = (unsigned long long)se.x | ((unsigned long long)(se.y - se.x) << 32); // {run start | rows << 32}
+  }
+#pragma unroll
+  for (int u = 0; u < DD_U; u++) {
+    const int64_t r = wbase + u * 64 + lane;
+    uint32_t c = 0;
+    if (r < n) {
+      c = (uint32_t)(m[u] >> 32);
+      __builtin_nontemporal_store(m[u], (unsigned long long *)(match + r));
+      if (outer_right && c == 0) c = 1;
+      if (!grouped) counts[r] = c;
+    }
+    if (grouped) {
+      const uint32_t wsum = wave_sum_u32(c);
+      if (lane == 0 && wbase + u * 64 < n) counts[(wbase + u * 64) >> 6] = wsum;
+    }
+  }
+}
+// The same pass in the shape of join_probe_dense_allhit_packed_kernel (persistent waves, 512 CONSECUTIVE rows per wave and trip,
+// 16-byte key loads and match stores): probe keys without NULLs in a 16-byte aligned column.  The lookups and the two streams
+// share the CU's vector memory path; this shape is what got the all-hit probe from 0.69 to 0.52 ms per 1e8 rows (tools/ubench2.hip).
+__global__ __launch_bounds__(256) void dd_count_stream_kernel(const uint64_t *__restrict__ keys, int64_t n, uint64_t kmin, uint64_t range,
+                                                              const uint32_t *__restrict__ table, int outer_right,
+                                                              uint32_t *__restrict__ counts, uint2 *__restrict__ match, int grouped) {
+  const int lane = lane_id();
+  const int64_t nchunks = n / JAP_ROWS, gw = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)),
+                nw = (int64_t)gridDim.x * 4;
+  const uint32_t miss = (uint32_t)range + 1;
+  for (int64_t c = gw; c < nchunks; c += nw) {
+    const int64_t r0 = c * JAP_ROWS + 2 * lane;
+    u64x2_vec k[4];
+    uint2_unaligned se[8];
+#pragma unroll
+    for (int g = 0; g < 4; g++) k[g] = __builtin_nontemporal_load((const u64x2_vec *)(keys + r0 + g * 128));
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+      const uint64_t d0 = k[g].x - kmin, d1 = k[g].y - kmin;
+      se[2 * g] = *(const uint2_unaligned *)(table + (d0 < range ? (uint32_t)d0 : miss));
+      se[2 * g + 1] = *(const uint2_unaligned *)(table + (d1 < range ? (uint32_t)d1 : miss));
+    }
+#pragma unroll
+    for (int g = 0; g < 4; g++) { // rows r0 + 128 g, + 1: lanes 2 l, 2 l + 1 of the 128-row piece
+      const uint32_t c0 = se[2 * g].y - se[2 * g].x, c1 = se[2 * g + 1].y - se[2 * g + 1].x;
+      u64x2_vec mv;
+      mv.x = (unsigned long long)se[2 * g].x | ((unsigned long long)c0 << 32);
+      mv.y = (unsigned long long)se[2 * g + 1].x | ((unsigned long long)c1 << 32);
+      __builtin_nontemporal_store(mv, (u64x2_vec *)(match + r0 + g * 128));
+      const uint32_t e0 = (outer_right && c0 == 0) ? 1u : c0, e1 = (outer_right && c1 == 0) ? 1u : c1;
+      if (grouped) { // two 64-row groups per piece: lanes 0-31 hold the first, 32-63 the second
+        uint32_t v = e0 + e1;
+        for (int m = 16; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
+        if ((lane & 31) == 0) counts[((c * JAP_ROWS + g * 128) >> 6) + (lane >> 5)] = v;
+      } else {
+        *(uint2 *)(counts + r0 + g * 128) = make_uint2(e0, e1);
+      }
+    }
+  }
+  if (gw == nchunks % nw) // the rows behind the last whole chunk (< 512, whole 64-row groups first): the wave whose turn it would be
+    for (int64_t rb = nchunks * JAP_ROWS; rb < n; rb += 64) {
+      const int64_t r = rb + lane;
+      uint32_t cv = 0;
+      if (r < n) {
+        const uint64_t d = keys[r] - kmin;
+        const uint2_unaligned e = *(const uint2_unaligned *)(table + (d < range ? (uint32_t)d : miss));
+        const uint32_t c0 = e.y - e.x;
+        match[r] = make_uint2(e.x, c0);
+        cv = (outer_right && c0 == 0) ? 1u : c0;
+        if (!grouped) counts[r] = cv;
+      }
+      if (grouped) {
+        const uint32_t wsum = wave_sum_u32(cv);
+        if (lane == 0) counts[rb >> 6] = wsum;
+      }
+    }
+}
+// build rows per key of a dense range with duplicates (join.hip, hash_join_dup_mult)
+__global__ void dup_mult_kernel(const uint64_t *__restrict__ keys, int64_t n, uint64_t kmin, uint32_t *__restrict__ mult) {
+  const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (r < n) atomicAdd(&mult[keys[r] - kmin], 1u);
+}
+// cut[i] = pairs whose probe row (right[], ascending: pairs are probe-row major) lies before bounds[i]
+__global__ void pairs_before_kernel(const uint32_t *__restrict__ right, int64_t m, const int64_t *__restrict__ bounds, int64_t n,
+                                    int64_t *__restrict__ cut) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t b = bounds[i];
+  int64_t lo = 0, hi = m; // first pair with right >= b
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((int64_t)right[mid] < b) lo = mid + 1;
+    else hi = mid;
+  }
+  cut[i] = lo;
 }
 
 } // namespace sq

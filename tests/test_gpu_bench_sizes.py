@@ -208,7 +208,7 @@ def test_full_size_c3_join_duplicate_build_keys(env, jt, keys):
     (+ one pair per unmatched probe row), probe-row major, build insertion order inside a probe row, equal keys on both sides,
     NULL left index exactly on the unmatched rows (hash_join.rs:172-177, 225-248).  `dense_range`: the same multiplicities over keys
     that fill 0 .. 2.5e5 (bench.py's C3_join_dup_build_keys_x4) — runs by key and one direct-address lookup per probe row
-    (join.hip: build_dense_dup), neither table."""
+    (join.hip: build_dense_dup, probe_counted), neither table."""
     t, abi, d = env.torch, env.abi, env.datagen
     from sqlrs_amd.expr import InputRef
     nP, nB, D = 100_000_000, 1_000_000, 250_000

@@ -147,7 +147,7 @@ def test_ab_hooks_give_the_same_pairs(hip, oracle, var, monkeypatch):
 @pytest.mark.parametrize("shape", ["all_hit", "half_hit", "duplicates", "too_sparse", "small_first_batch", "null_probe_keys"])
 def test_first_probe_against_the_device_side_verdict(hip, oracle, shape):
     """build_finish leaves the direct-address build's verdict on the device; the first probe batch runs the optimistic
-    all-hit kernel against it and fetches both answers together (join.hip, dense_resolve).  Every outcome of that pair —
+    all-hit kernel against it and fetches both answers together (join.hip, probe_allhit_pending).  Every outcome of that pair —
     dense + all hit, dense + misses, duplicates, range too wide — and the first batches that cannot take the kernel (small,
     NULL keys: the verdict is fetched first), each followed by a second batch; pairs in hash_join.rs:217-253 order."""
     rng = np.random.default_rng(len(shape))

@@ -37,7 +37,7 @@ What no input of <= 2^18 rows reaches, and the condition in the source that keep
 * the `range < 2^31` bound of the direct-address table (dense_range.hpp: `span < 2^31 - 1`): a range is admitted up to 4 x rows +
   1024 (16 x rows for a join+aggregate's join), so the bound decides only from 2^29 build rows on.  host/dense_range_check.cpp
   puts the decision itself through both sides of it (test_join_model_cpu.py);
-* per-row pair counts CHOSEN by size (join.hip probe_pairs: `j->nB < (1ll << 26)`): reached here only through
+* per-row pair counts CHOSEN by size (join.hip probe_counted: `j->nB < (1ll << 26)`): reached here only through
   SQLRS_JOIN_GROUPED=0, which selects the same kernels' per-row form on every count route;
 * a pair total beyond 2^32 (the 64-bit offsets of the fill pass; the `n > 0xffffffff` guards): 5 000 x 70 001 pairs would already
   be 3.5e8, the cases stay under 2^18 pairs per batch;
@@ -109,8 +109,11 @@ def route(be, label, plan):
 
 
 class Plan:
-    """the host-side dispatch of build_table / dense_resolve / probe_pairs (join.hip) and lds_build_first / lds_join_match
-    (join_lds.hip), restated over the facts of a case: which counters and scopes a run must move"""
+    """the host-side dispatch of join.hip and lds_build_first / lds_join_match (join_lds.hip), restated over the facts of a case:
+    which counters and scopes a run must move.  build = build_table (dense_try_one_fetch / dense_try_two_fetch), verdict =
+    dense_verdict_decide + dense_apply_verdict, resolve = dense_resolve, after_refusal = build_after_refusal, ensure_table =
+    hash_join_ensure_table, probe = probe_pairs and the route functions it chooses (probe_allhit_pending, probe_unique_inner,
+    probe_unique_outer, probe_counted)"""
 
     def __init__(self, facts, jt, env=None, lazy=False, key_only_semi=False, slots_per_key=None):
         self.f, self.jt, self.env = facts, jt, env or {}
