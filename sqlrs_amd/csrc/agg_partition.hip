@@ -218,6 +218,11 @@ struct LdsAggParams {
   int seg_off; // SQLRS_AGG_SEG=0 (read per call): no per-run adds for ordered rows (lds_agg_dense_slim_kernel; A/B)
 };
 
+// one group as the dense bucket passes store it for a caller that only orders and emits (PartAggOutput::grow)
+struct alignas(32) GroupRow {
+  unsigned long long key, cell0, cell1, first;
+};
+
 // cell of accumulator `kind` for a key that has `m` build rows (every probe row = m joined rows)
 __device__ __forceinline__ unsigned long long acc_times(int kind, unsigned long long cell, unsigned int m) {
   switch (kind) {
@@ -651,7 +656,7 @@ constexpr int SED_SLOTS = 16, SED_GROUPS = 16;
 __global__ __launch_bounds__(SED_SLOTS * SED_GROUPS) void split_emit_dense_kernel(
     SplitTables stb, const uint32_t *__restrict__ split_bucket, const uint32_t *__restrict__ chunk_lo, uint32_t nbuckets_split,
     uint32_t R, KeyPack kp, LdsAggParams prm, int n_acc, unsigned long long *out_count, uint64_t *__restrict__ gkey,
-    uint32_t *__restrict__ gfirst, uint64_t *__restrict__ gacc, int64_t gcap) {
+    uint32_t *__restrict__ gfirst, uint64_t *__restrict__ gacc, int64_t gcap, GroupRow *__restrict__ grow) {
   __shared__ unsigned int s_first[SED_GROUPS][SED_SLOTS];
   __shared__ unsigned long long s_acc[PART_MAX_ACC][SED_GROUPS][SED_SLOTS];
   const uint32_t tiles_per_bucket = (R + SED_SLOTS - 1) / SED_SLOTS;
@@ -706,16 +711,24 @@ __global__ __launch_bounds__(SED_SLOTS * SED_GROUPS) void split_emit_dense_kerne
   if (prm.partner_mult) mlt = prm.partner_mult[((uint64_t)split_bucket[t] << kp.rbits) + s]; // (> 0: the chunk tables hold partners only)
   unsigned long long base = atomicAdd(out_count, 1ull);
   if ((int64_t)base >= gcap) return;
-  gkey[base] = kp.kmin + ((uint64_t)split_bucket[t] << kp.rbits) + s;
   gfirst[base] = first;
-  for (int a = 0; a < n_acc; a++) gacc[(size_t)a * gcap + base] = prm.partner_mult ? acc_times(prm.code[a] & 7, acc[a], mlt) : acc[a];
+  if (prm.partner_mult)
+    for (int a = 0; a < n_acc; a++) acc[a] = acc_times(prm.code[a] & 7, acc[a], mlt);
+  const uint64_t key = kp.kmin + ((uint64_t)split_bucket[t] << kp.rbits) + s;
+  if (grow) {
+    grow[base] = GroupRow{key, acc[0], n_acc > 1 ? acc[1] : 0ull, first};
+    return;
+  }
+  gkey[base] = key;
+  for (int a = 0; a < n_acc; a++) gacc[(size_t)a * gcap + base] = acc[a];
 }
 
 template <int NV, bool JOIN, int NACC, int C0, int C1, bool REC = false>
 __global__ __launch_bounds__(DENSE_WG) void lds_agg_dense_kernel(
     LdsAggParams prm, const uint64_t *__restrict__ pk, const uint64_t *__restrict__ pv0,
     const uint32_t *__restrict__ work, unsigned long long *out_count, uint64_t *__restrict__ gkey,
-    uint32_t *__restrict__ gfirst, uint64_t *__restrict__ gacc, int64_t gcap, KeyPack kp, SplitTables stb) {
+    uint32_t *__restrict__ gfirst, uint64_t *__restrict__ gacc, int64_t gcap, KeyPack kp, SplitTables stb,
+    GroupRow *__restrict__ grow) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long tab[];
   __shared__ unsigned int s_cnt;
   __shared__ unsigned long long s_base;
@@ -887,14 +900,25 @@ __global__ __launch_bounds__(DENSE_WG) void lds_agg_dense_kernel(
     unsigned int first = tfirst[s];
     if (first == 0xffffffffu) continue;
     if ((int64_t)base < gcap) {
-      gkey[base] = key0 + s;
       gfirst[base] = first;
       const unsigned int mlt = (JOIN && prm.partner_mult) ? prm.partner_mult[((uint64_t)b << kp.rbits) + s] : 1u;
+      if (grow) { // (n_acc <= 2: PartAggInput::want_group_rows)
+        unsigned long long c[2] = {0, 0};
 #pragma unroll
-      for (int a = 0; a < PART_MAX_ACC; a++) {
-        if (a >= n_acc) break;
-        const unsigned long long cell = tacc[(size_t)a * R + s];
-        gacc[(size_t)a * gcap + base] = (JOIN && prm.partner_mult) ? acc_times(code_of(a) & 7, cell, mlt) : cell;
+        for (int a = 0; a < 2; a++) {
+          if (a >= n_acc) break;
+          const unsigned long long cell = tacc[(size_t)a * R + s];
+          c[a] = (JOIN && prm.partner_mult) ? acc_times(code_of(a) & 7, cell, mlt) : cell;
+        }
+        grow[base] = GroupRow{key0 + s, c[0], c[1], first};
+      } else {
+        gkey[base] = key0 + s;
+#pragma unroll
+        for (int a = 0; a < PART_MAX_ACC; a++) {
+          if (a >= n_acc) break;
+          const unsigned long long cell = tacc[(size_t)a * R + s];
+          gacc[(size_t)a * gcap + base] = (JOIN && prm.partner_mult) ? acc_times(code_of(a) & 7, cell, mlt) : cell;
+        }
       }
     }
     base++;
@@ -930,7 +954,7 @@ template <bool JOIN, int NACC, int C0, int C1, bool BLK = false>
 __global__ __launch_bounds__(DENSE_WG) void lds_agg_dense_slim_kernel(
     LdsAggParams prm, SlimBucketIn in, const uint32_t *__restrict__ work, unsigned long long *out_count,
     uint64_t *__restrict__ gkey, uint32_t *__restrict__ gfirst, uint64_t *__restrict__ gacc, int64_t gcap, KeyPack kp,
-    SplitTables stb) {
+    SplitTables stb, GroupRow *__restrict__ grow) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long tab[];
   __shared__ unsigned int s_cnt, s_before, s_inside;
   __shared__ unsigned long long s_base;
@@ -1270,14 +1294,25 @@ __global__ __launch_bounds__(DENSE_WG) void lds_agg_dense_slim_kernel(
     unsigned int first = tfirst[s];
     if (first == 0xffffffffu) continue;
     if ((int64_t)obase < gcap) {
-      gkey[obase] = key0 + s;
       gfirst[obase] = first;
       const unsigned int mlt = (JOIN && prm.partner_mult) ? prm.partner_mult[((uint64_t)b << kp.rbits) + s] : 1u;
+      if (grow) { // (n_acc <= 2: PartAggInput::want_group_rows)
+        unsigned long long c[2] = {0, 0};
 #pragma unroll
-      for (int a = 0; a < PART_MAX_ACC; a++) {
-        if (a >= n_acc) break;
-        const unsigned long long cell = tacc[(size_t)a * R + s];
-        gacc[(size_t)a * gcap + obase] = (JOIN && prm.partner_mult) ? acc_times(code_of(a) & 7, cell, mlt) : cell;
+        for (int a = 0; a < 2; a++) {
+          if (a >= n_acc) break;
+          const unsigned long long cell = tacc[(size_t)a * R + s];
+          c[a] = (JOIN && prm.partner_mult) ? acc_times(code_of(a) & 7, cell, mlt) : cell;
+        }
+        grow[obase] = GroupRow{key0 + s, c[0], c[1], first};
+      } else {
+        gkey[obase] = key0 + s;
+#pragma unroll
+        for (int a = 0; a < PART_MAX_ACC; a++) {
+          if (a >= n_acc) break;
+          const unsigned long long cell = tacc[(size_t)a * R + s];
+          gacc[(size_t)a * gcap + obase] = (JOIN && prm.partner_mult) ? acc_times(code_of(a) & 7, cell, mlt) : cell;
+        }
       }
     }
     obase++;
@@ -1288,6 +1323,15 @@ __global__ void first_to_rowid_kernel(const uint32_t *__restrict__ gfirst, int64
                                       uint64_t *__restrict__ out) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i < n) out[i] = offset + gfirst[i];
+}
+__global__ void group_rows_to_columns_kernel(const GroupRow *__restrict__ grow, int64_t n, int n_acc, int64_t gcap,
+                                             uint64_t *__restrict__ gkey, uint64_t *__restrict__ gacc) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const GroupRow r = grow[i];
+  gkey[i] = r.key;
+  gacc[i] = r.cell0;
+  if (n_acc > 1) gacc[gcap + i] = r.cell1;
 }
 __global__ void bytes_pack_kernel(const uint8_t *__restrict__ bytes, int64_t n, uint64_t *__restrict__ out) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -1333,6 +1377,18 @@ const uint64_t *part_row_ids(Ctx *ctx, PartAggOutput &po) {
     }
   }
   return po.row_ids->as<uint64_t>();
+}
+
+void part_group_columns(Ctx *ctx, PartAggOutput &po, int n_acc) {
+  if (!po.grow) return;
+  po.gkey = ctx->alloc(8 * (size_t)po.gcap);
+  po.gacc = ctx->alloc(8 * (size_t)po.gcap * (size_t)std::max(n_acc, 1));
+  if (po.groups) {
+    group_rows_to_columns_kernel<<<dim3((unsigned)ceil_div(po.groups, 256)), dim3(256), 0, ctx->stream>>>(
+        po.grow->as<GroupRow>(), po.groups, n_acc, po.gcap, po.gkey->as<uint64_t>(), po.gacc->as<uint64_t>());
+    SQ_HIP(hipGetLastError());
+  }
+  po.grow = nullptr;
 }
 
 bool partitioned_preaggregate(Ctx *ctx, const PartAggSpec &spec, const PartAggInput &in,
@@ -1663,11 +1719,16 @@ bool partitioned_preaggregate(Ctx *ctx, const PartAggSpec &spec, const PartAggIn
     split_init_kernel<<<dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, ctx->stream>>>(stb, total, spec.n_acc, prm);
     SQ_HIP(hipGetLastError());
   }
-  out->gkey = ctx->alloc(8 * (size_t)gcap);
+  // (group rows: the three dense kernels only, which have no NULL key; one or two cells)
+  const bool group_rows = in.want_group_rows && dense && !in.key_validity && spec.n_acc >= 1 && spec.n_acc <= 2;
   out->gfirst = ctx->alloc(4 * (size_t)gcap);
   out->gvalid = in.key_validity ? ctx->alloc((size_t)gcap) : nullptr;
-  out->gacc = ctx->alloc(8 * (size_t)gcap * (size_t)std::max(spec.n_acc, 1));
+  out->grow = group_rows ? ctx->alloc(sizeof(GroupRow) * (size_t)gcap) : nullptr;
+  out->gkey = group_rows ? nullptr : ctx->alloc(8 * (size_t)gcap);
+  out->gacc = group_rows ? nullptr : ctx->alloc(8 * (size_t)gcap * (size_t)std::max(spec.n_acc, 1));
   out->gcap = gcap;
+  GroupRow *const grow = group_rows ? out->grow->as<GroupRow>() : nullptr;
+  uint64_t *const gkey = group_rows ? nullptr : out->gkey->as<uint64_t>(), *const gacc = group_rows ? nullptr : out->gacc->as<uint64_t>();
   if (!out->ov_rows) out->ov_rows = ctx->alloc(4 * (size_t)std::max<int64_t>(n, 1)); // (n: rows that passed the fused filter)
   // (route witnesses: the form of this bucket pass, common.hpp Ctx::AggRoute; the kernel family is counted at its launch)
   ctx->agg_route[pr.pack.kbits ? Ctx::AR_PACKED : Ctx::AR_UNPACKED]++;
@@ -1730,8 +1791,7 @@ bool partitioned_preaggregate(Ctx *ctx, const PartAggSpec &spec, const PartAggIn
     if (blk) kfn = lds_agg_dense_slim_kernel<JN, NA, C0, C1, true>;                                             \
     allow_big_lds(ctx, kfn, 159 * 1024);                                                                                 \
     kfn<<<dim3(nwork), dim3(DENSE_WG), slds, ctx->stream>>>(prm, sb, dwork->as<uint32_t>(), ctr->as<unsigned long long>(), \
-                                                           out->gkey->as<uint64_t>(), out->gfirst->as<uint32_t>(), \
-                                                           out->gacc->as<uint64_t>(), gcap, pr.pack, stb);        \
+                                                           gkey, out->gfirst->as<uint32_t>(), gacc, gcap, pr.pack, stb, grow); \
     ctx->agg_route[blk ? Ctx::AR_SLIM_BLK : Ctx::AR_SLIM_RUNS]++;                                              \
     ctx->agg_route[Ctx::AR_INTERPRETED] += NA < 0;                                                             \
     launched = true;                                                                                           \
@@ -1748,7 +1808,7 @@ bool partitioned_preaggregate(Ctx *ctx, const PartAggSpec &spec, const PartAggIn
       if (nsplit) {
         split_emit_dense_kernel<<<dim3((unsigned)(nsplit * ceil_div((int64_t)nslots_h, SED_SLOTS))), dim3(SED_SLOTS * SED_GROUPS), 0, ctx->stream>>>(
             stb, dsplit->as<uint32_t>(), dchunk_lo->as<uint32_t>(), nsplit, cap, pr.pack, prm, spec.n_acc,
-            ctr->as<unsigned long long>(), out->gkey->as<uint64_t>(), out->gfirst->as<uint32_t>(), out->gacc->as<uint64_t>(), gcap);
+            ctr->as<unsigned long long>(), gkey, out->gfirst->as<uint32_t>(), gacc, gcap, grow);
       }
     } else if (dense) { // direct-addressed tables (packed rows, nothing nullable, at most one value column)
 #define SQ_LD(NV, JN, NA, C0, C1)                                                                              \
@@ -1758,8 +1818,7 @@ bool partitioned_preaggregate(Ctx *ctx, const PartAggSpec &spec, const PartAggIn
     allow_big_lds(ctx, kfn);                                                                                   \
     kfn<<<dim3(nwork), dim3(DENSE_WG), lds, ctx->stream>>>(                                                    \
         prm, pr.rec ? pr.rec->as<uint64_t>() : pk->as<uint64_t>(), pv0 ? pv0->as<uint64_t>() : nullptr, dwork->as<uint32_t>(), \
-        ctr->as<unsigned long long>(), out->gkey->as<uint64_t>(), out->gfirst->as<uint32_t>(),                 \
-        out->gacc->as<uint64_t>(), gcap, pr.pack, stb);                                                        \
+        ctr->as<unsigned long long>(), gkey, out->gfirst->as<uint32_t>(), gacc, gcap, pr.pack, stb, grow);     \
     ctx->agg_route[Ctx::AR_DENSE]++;                                                                           \
     ctx->agg_route[Ctx::AR_INTERPRETED] += NA < 0;                                                             \
     launched = true;                                                                                           \
@@ -1783,7 +1842,7 @@ bool partitioned_preaggregate(Ctx *ctx, const PartAggSpec &spec, const PartAggIn
       if (nsplit) {
         split_emit_dense_kernel<<<dim3((unsigned)(nsplit * ceil_div((int64_t)nslots_h, SED_SLOTS))), dim3(SED_SLOTS * SED_GROUPS), 0, ctx->stream>>>(
             stb, dsplit->as<uint32_t>(), dchunk_lo->as<uint32_t>(), nsplit, cap, pr.pack, prm, spec.n_acc,
-            ctr->as<unsigned long long>(), out->gkey->as<uint64_t>(), out->gfirst->as<uint32_t>(), out->gacc->as<uint64_t>(), gcap);
+            ctr->as<unsigned long long>(), gkey, out->gfirst->as<uint32_t>(), gacc, gcap, grow);
       }
     }
     // specialised kernels: no nullable column, one value column, the usual accumulator lists

@@ -55,6 +55,9 @@ struct PartAggInput {
   RowFilter filter;
   // true: key statistics from a full pass (the rerun after an optimistic attempt saw a key outside its sampled range)
   bool exact_stats = false;
+  // the caller will only order the groups by first row and emit key + cells (hashagg_op.hip emit_pending) and the list has at
+  // most two COUNT / SUM cells: a dense bucket pass may then store each group as ONE 32-byte row (PartAggOutput::grow)
+  bool want_group_rows = false;
 };
 
 // Groups of ONE batch: key, first row (local index), one 8-byte cell per accumulator
@@ -62,6 +65,10 @@ struct PartAggInput {
 struct PartAggOutput {
   int64_t groups = 0, gcap = 0;
   BufP gkey, gfirst, gvalid, gvalid_bits, gacc;
+  // set instead of gkey / gacc (PartAggInput::want_group_rows, dense bucket passes): gcap rows {key, cell 0, cell 1 (0 when
+  // the list has one cell), first row}, 32 bytes each and aligned — what ordering the groups reads at random is one aligned
+  // row per group, not three columns.  gfirst is written as well.  part_group_columns() turns the rows into gkey / gacc.
+  BufP grow;
   BufP row_ids;            // gfirst as global row numbers (u64): made on demand, part_row_ids()
   uint64_t row_offset = 0; // global row number of the batch's row 0
   int64_t n_overflow = 0; // rows that did not fit their bucket table
@@ -77,6 +84,8 @@ struct PartAggOutput {
 // first rows of the groups as global row numbers (row_offset + gfirst), made on first use: only a merge into an existing
 // aggregation state needs them; a single batch's groups are ordered by the local u32 first rows as they are
 const uint64_t *part_row_ids(Ctx *ctx, PartAggOutput &po);
+// gkey / gacc from grow (n_acc cells), for a batch that is merged into an aggregation state after all; grow is dropped
+void part_group_columns(Ctx *ctx, PartAggOutput &po, int n_acc);
 // also returns min / max of the valid keys' signed-order image (key ^ 1 << 63) when asked
 double estimate_distinct(Ctx *ctx, const uint64_t *keys, const uint64_t *validity, int64_t n,
                          uint64_t *omin = nullptr, uint64_t *omax = nullptr, bool *sampled = nullptr);

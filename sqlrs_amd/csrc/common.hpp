@@ -175,6 +175,7 @@ struct Ctx {
     AR_MERGE_GROUPS, // hashagg_op: pre-aggregated groups merged into the table state with weights
     AR_PENDING,      // hashagg_op: a pre-aggregated batch deferred as the operator's whole state
     AR_WIDE_PARTS,   // hashagg_op: partition-route operators a wide aggregate list was run as (per pushed batch)
+    AR_ORDER_PACKED, // hashagg_op: pending groups stored as 32-byte rows and ordered by a sort whose last pass gathers them
     AR_COUNT_
   };
   int64_t agg_route[AR_COUNT_] = {};

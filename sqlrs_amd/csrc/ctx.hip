@@ -1479,7 +1479,7 @@ int sqlrs_ctx_profile_read(sqlrs_ctx_t *ctx, int cap, const char **names, double
       "agg_part_dense", "agg_part_slim_runs", "agg_part_slim_blk", "agg_part_probe_spec", "agg_part_probe_generic",
       "agg_part_interpreted", "agg_part_packed", "agg_part_unpacked", "agg_part_flags", "agg_part_rec",
       "agg_part_in_place", "agg_part_join", "agg_part_join_mult", "agg_part_split", "agg_part_overflow_rows",
-      "agg_merge_groups", "agg_pending_deferred", "agg_wide_parts"};
+      "agg_merge_groups", "agg_pending_deferred", "agg_wide_parts", "agg_order_packed"};
   for (int r = 0; r < Ctx::AR_COUNT_; r++) {
     if (!ctx->agg_route[r]) continue;
     if (n < cap) {

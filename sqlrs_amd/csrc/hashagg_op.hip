@@ -60,7 +60,8 @@ bool same_expr(const Expr &x, const Expr &y) {
 struct PendingGroups {
   bool active = false;
   PartAggOutput po;
-  std::vector<DCol> keyvals;          // key column values per group (list order)
+  std::vector<DCol> keyvals;          // key column values per group (list order); empty while the groups are rows (po.grow)
+  int n_acc = 0;                      // cells per group
   std::vector<int> cnt_of_col, acc_of_agg, col_of_agg;
   std::vector<uint8_t> col_nullable;  // value column carried NULLs in that batch
   std::vector<int32_t> col_dtype;
@@ -342,11 +343,71 @@ static void merge_groups(sqlrs_hash_agg *a, PendingGroups &pg) {
   }
 }
 
+// the one exactly-compared 8-byte key column of a batch's groups: the normalised key IS the value
+static DCol group_key_column(const PartAggOutput &po, int32_t dtype) {
+  DCol kv;
+  kv.dtype = dtype;
+  kv.length = po.groups;
+  kv.values = po.gkey->p;
+  kv.own_values = po.gkey;
+  if (po.gvalid_bits) {
+    kv.validity = po.gvalid_bits->as<uint64_t>();
+    kv.own_validity = po.gvalid_bits;
+    kv.null_count = -1;
+  }
+  return kv;
+}
+
+// groups stored as 32-byte rows (PartAggOutput::grow) back into the column form everything but emit_pending reads
+static void group_rows_to_columns(sqlrs_hash_agg *a, PendingGroups &pg) {
+  if (!pg.po.grow) return;
+  part_group_columns(a->ctx, pg.po, pg.n_acc);
+  pg.keyvals.push_back(group_key_column(pg.po, pg.key_dtype));
+}
+
 static void flush_pending(sqlrs_hash_agg *a) {
   if (!a->pending.active) return;
   PendingGroups pg = std::move(a->pending);
   a->pending = PendingGroups();
+  group_rows_to_columns(a, pg);
   merge_groups(a, pg);
+}
+
+// emit_pending over group rows: ONE ordering that leaves the output columns — the passes of radix_sort_index_u32 over the
+// first rows, the last of which gathers each position's row into the key / aggregate columns (no packing pass, no
+// permutation in memory, no separate gather).  COUNT / SUM cells only, nothing nullable (agg_consume asked for rows only then).
+static DBatch emit_pending_group_rows(sqlrs_hash_agg *a) {
+  Ctx *ctx = a->ctx;
+  PendingGroups &pg = a->pending;
+  PartAggOutput &po = pg.po;
+  const int64_t G = po.groups;
+  ProfScope ps(ctx, "agg_order_groups");
+  ctx->agg_route[Ctx::AR_ORDER_PACKED]++;
+  DBatch o;
+  o.rows = G;
+  auto column = [&](int32_t dtype) {
+    DCol c;
+    c.dtype = dtype;
+    c.length = G;
+    c.own_values = ctx->alloc(8 * (size_t)G);
+    c.values = c.own_values->p;
+    return c;
+  };
+  SortedRowsOut ro;
+  ro.rows = po.grow->as<uint64_t>();
+  o.cols.push_back(column(pg.key_dtype));
+  ro.key = (uint64_t *)o.cols.back().values;
+  for (size_t i = 0; i < a->aggs.size(); i++) {
+    const AggSpec &s = a->aggs[i];
+    const bool count = s.func == SQLRS_AGG_COUNT;
+    o.cols.push_back(column(count ? SQLRS_INT64 : s.return_dtype));
+    ro.agg[i] = (uint64_t *)o.cols.back().values;
+    ro.cell[i] = count ? pg.cnt_of_col[(size_t)pg.col_of_agg[i]] : pg.acc_of_agg[i];
+  }
+  int bits = 1;
+  while (bits < 32 && (1ull << bits) <= (uint64_t)std::max<int64_t>(a->rows_seen, 1)) bits++;
+  radix_sort_gather_rows_u32(ctx, po.gfirst->as<uint32_t>(), G, bits, ro);
+  return o;
 }
 
 // finish() when one pre-aggregated batch is the whole input: emit its cells directly
@@ -355,6 +416,8 @@ static DBatch emit_pending(sqlrs_hash_agg *a) {
   PendingGroups &pg = a->pending;
   PartAggOutput &po = pg.po;
   int64_t G = po.groups;
+  if (po.grow && G > 0) return emit_pending_group_rows(a);
+  group_rows_to_columns(a, pg);
   DBatch o;
   o.rows = G;
   for (const DCol &k : pg.keyvals) o.cols.push_back(k);
@@ -602,6 +665,16 @@ static bool agg_consume(sqlrs_hash_agg *a, int64_t n, const std::vector<DCol> &k
           pin.join_mult = js->mult;
         }
         if (rf) pin.filter = *rf;
+        // Groups as 32-byte rows for emit_pending_group_rows: this batch may be the operator's whole input, its output is
+        // ordered by first row, and a group is one 8-byte key value + one or two COUNT / SUM cells without NULLs.
+        const char *rows_e = hook("SQLRS_AGG_ORDER_PACKED"); // A/B hook, read per call: 0 = groups as columns, ordered by pack + sort + gather
+        const bool key_is_value = nk.exact && kcols.size() == 1 && (kcols[0].dtype == SQLRS_INT64 || kcols[0].dtype == SQLRS_FLOAT64) &&
+                                  kcols[0].dtype == nk.dtype;
+        bool rows_ok = !(rows_e && rows_e[0] == '0') && !a->any_order && a->st.ngroups == 0 && !a->pending.active && key_is_value && !nk.validity &&
+                       !a->aggs.empty() && a->aggs.size() <= 2 && spec.n_acc <= 2;
+        for (const AggSpec &s : a->aggs) rows_ok &= s.func == SQLRS_AGG_COUNT || s.func == SQLRS_AGG_SUM;
+        for (size_t k = 0; k < pcols.size(); k++) rows_ok &= pin.val_validity[k] == nullptr;
+        pin.want_group_rows = rows_ok;
         PartAggOutput po;
         flush_pending(a); // an older deferred batch must be in the table before this one
         bool part_ok = partitioned_preaggregate(ctx, spec, pin, (uint64_t)a->rows_seen, &po);
@@ -615,6 +688,7 @@ static bool agg_consume(sqlrs_hash_agg *a, int64_t n, const std::vector<DCol> &k
           pg.active = true;
           pg.exact = nk.exact;
           pg.key_dtype = nk.dtype;
+          pg.n_acc = spec.n_acc;
           pg.cnt_of_col = cnt_of_col;
           pg.acc_of_agg = acc_of_agg;
           for (const AggSpec &s : a->aggs) pg.col_of_agg.push_back(pidx[(size_t)s.argcol]);
@@ -625,25 +699,18 @@ static bool agg_consume(sqlrs_hash_agg *a, int64_t n, const std::vector<DCol> &k
           // key values of every group of the batch (hash_agg.rs:90-96).  One exactly-compared 8-byte
           // key column: the normalised key IS the value (int64 / f64 bit pattern), no gather needed
           // (a random gather of 1e7 keys costs 0.25 ms)
-          if (nk.exact && kcols.size() == 1 && (kcols[0].dtype == SQLRS_INT64 || kcols[0].dtype == SQLRS_FLOAT64) &&
-              kcols[0].dtype == nk.dtype) {
-            DCol kv;
-            kv.dtype = kcols[0].dtype;
-            kv.length = po.groups;
-            kv.values = po.gkey->p;
-            kv.own_values = po.gkey;
-            if (po.gvalid_bits) {
-              kv.validity = po.gvalid_bits->as<uint64_t>();
-              kv.own_validity = po.gvalid_bits;
-              kv.null_count = -1;
-            }
-            pg.keyvals.push_back(kv);
+          const bool defer = a->st.ngroups == 0 && po.n_overflow == 0 && !po.may_dup;
+          if (!defer) part_group_columns(ctx, po, spec.n_acc); // (merged below: columns)
+          if (po.grow) {
+            // (the key column comes out of the ordering, or of group_rows_to_columns when a later batch arrives)
+          } else if (key_is_value) {
+            pg.keyvals.push_back(group_key_column(po, kcols[0].dtype));
           } else {
             for (const DCol &kc : kcols)
               pg.keyvals.push_back(gather_column(ctx, kc, po.gfirst->p, false, nullptr, po.groups));
           }
           pg.po = po;
-          if (a->st.ngroups == 0 && po.n_overflow == 0 && !po.may_dup) {
+          if (defer) {
             a->pending = std::move(pg); // nothing to merge with yet: defer building the table
             ctx->agg_route[Ctx::AR_PENDING]++;
           } else

@@ -105,6 +105,16 @@ void radix_sort_pairs(Ctx *ctx, uint64_t *keys, uint32_t *vals, int64_t n, int b
                       int end_bit, bool keys_below_end_bit = false);
 // perm[0 .. n) = the indices 0 .. n-1 in the stable order of their u32 keys (all below 2^bits)
 void radix_sort_index_u32(Ctx *ctx, const uint32_t *keys, int64_t n, int bits, uint32_t *perm);
+// The same passes, but the last one writes no permutation: output position g receives the columns of row perm[g] of `rows`,
+// 32-byte group rows {key, cell 0, cell 1, first row} (agg_partition.hpp PartAggOutput::grow): key[g] = the key and
+// agg[c][g] = cell cell[c] (agg[1] may be null).  COUNT / SUM cells are final as they are stored (agg_finalize_raw copies them).
+struct SortedRowsOut {
+  const uint64_t *rows = nullptr;
+  uint64_t *key = nullptr;
+  uint64_t *agg[2] = {nullptr, nullptr};
+  int cell[2] = {0, 0};
+};
+void radix_sort_gather_rows_u32(Ctx *ctx, const uint32_t *keys, int64_t n, int bits, const SortedRowsOut &ro);
 void iota_u32(Ctx *ctx, uint32_t *out, int64_t n);
 // order_fast.hip: ORDER BY one fixed-width key without NULLs, rows (key, one carried 8-byte column, row id)
 // travel through <= 2 HBM passes + an in-LDS finish; false = shape / data do not fit (general path)

@@ -53,12 +53,17 @@ __global__ __launch_bounds__(RS_WG) void rs_hist_kernel(const uint64_t *__restri
 // a PACKED -> PAIR pass rebuilds the key as (word >> 32) << key_lo | key_const.
 // KEY32 (with IN = RS_PAIR): `keys` is an array of u32 keys and a row's value is its index (no `vals` array): the first
 // pass of radix_sort_index_u32.  keys_out == nullptr (OUT = RS_PAIR): only the values are written (its last pass).
-enum { RS_PAIR = 0, RS_PACKED = 1 };
+// OUT = RS_ROWS (IN = RS_PACKED: the last pass of radix_sort_gather_rows_u32): no record leaves at
+// all — output position g receives the columns of the 32-byte row its record's low word names (`ro`, prims.hpp).
+enum { RS_PAIR = 0, RS_PACKED = 1, RS_ROWS = 2 };
+struct alignas(16) RsRowHalf {
+  uint64_t a, b;
+};
 template <int IN, int OUT, bool KEY32 = false>
 __global__ __launch_bounds__(RS_WG) void rs_scatter_kernel(
     const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals, int64_t n, int shift,
     int64_t nblocks, const uint32_t *__restrict__ offsets, uint64_t *__restrict__ keys_out,
-    uint32_t *__restrict__ vals_out, int key_lo, uint64_t key_const) {
+    uint32_t *__restrict__ vals_out, int key_lo, uint64_t key_const, SortedRowsOut ro = SortedRowsOut()) {
   __shared__ uint64_t skey[RS_TILE];
   __shared__ uint32_t sval[(IN == RS_PAIR && OUT == RS_PAIR) ? RS_TILE : 1];
   __shared__ uint32_t wcnt[RS_WAVES][256];
@@ -148,7 +153,14 @@ __global__ __launch_bounds__(RS_WG) void rs_scatter_kernel(
       // digit of the staged record: a freshly packed word carries the key at bit 32 - key_lo
       const int sh = (IN == RS_PAIR && OUT == RS_PACKED) ? shift - key_lo + 32 : shift;
       const int64_t g = gbase[(uint32_t)(kk >> sh) & 255u] + p;
-      if (OUT == RS_PACKED) {
+      if (OUT == RS_ROWS) {
+        // (the random read the gather did, now one aligned 32-byte row; the stores run over consecutive g like the records')
+        const RsRowHalf *row = (const RsRowHalf *)(ro.rows + 4 * (size_t)(uint32_t)kk);
+        const RsRowHalf lo = row[0], hi = row[1]; // {key, cell 0}, {cell 1, first row}
+        ro.key[g] = lo.a;
+        ro.agg[0][g] = ro.cell[0] ? hi.a : lo.b;
+        if (ro.agg[1]) ro.agg[1][g] = ro.cell[1] ? hi.a : lo.b;
+      } else if (OUT == RS_PACKED) {
         keys_out[g] = kk;
       } else if (IN == RS_PACKED) {
         if (keys_out) keys_out[g] = ((kk >> 32) << key_lo) | key_const;
@@ -267,11 +279,13 @@ void radix_sort_pairs(Ctx *ctx, uint64_t *keys, uint32_t *vals, int64_t n, int b
 // perm = the row indices 0 .. n-1 ordered by their u32 key (stable), keys below 2^bits: the ordering of an aggregation's
 // groups by first row (hash_agg.rs:98) without widening the keys to u64, without an iota array and without sorted keys
 // coming back — the first pass reads the u32 keys and packs (key << 32 | index) words, the last writes the indices only.
-void radix_sort_index_u32(Ctx *ctx, const uint32_t *keys, int64_t n, int bits, uint32_t *perm) {
+// `ro` set: the last pass gathers the rows instead of writing `perm` (radix_sort_gather_rows_u32).  It reads packed words, so
+// keys below 2^8 take two passes there (the second over a digit that is zero everywhere: stable, the identity).
+static void sort_index_u32(Ctx *ctx, const uint32_t *keys, int64_t n, int bits, uint32_t *perm, const SortedRowsOut *ro) {
   if (n <= 0) return;
   if (n > 0xffffffffll) fail(SQLRS_ERR_INTERNAL, "radix sort: more than 2^32 rows");
   ProfScope ps(ctx, "radix_sort");
-  const int passes = std::max(1, (std::min(bits, 32) + 7) / 8);
+  const int passes = std::max(ro ? 2 : 1, (std::min(bits, 32) + 7) / 8);
   const int64_t nblocks = ceil_div(n, RS_TILE);
   BufP w0 = ctx->alloc(8 * (size_t)n), w1 = passes > 2 ? ctx->alloc(8 * (size_t)n) : nullptr;
   BufP hist = ctx->alloc(4 * (size_t)(256 * nblocks)), offs = ctx->alloc(4 * (size_t)(256 * nblocks));
@@ -286,7 +300,9 @@ void radix_sort_index_u32(Ctx *ctx, const uint32_t *keys, int64_t n, int bits, u
     else rs_hist_kernel<false><<<g, b, 0, ctx->stream>>>(in, n, shift, nblocks, hist->as<uint32_t>());
     SQ_HIP(hipGetLastError());
     exclusive_scan_u32(ctx, hist->as<uint32_t>(), 256 * nblocks, nullptr, offs->as<uint32_t>(), total->as<uint64_t>());
-    if (first && last)
+    if (last && ro)
+      rs_scatter_kernel<RS_PACKED, RS_ROWS><<<g, b, 0, ctx->stream>>>(in, nullptr, n, shift, nblocks, offs->as<uint32_t>(), nullptr, nullptr, 0, 0, *ro);
+    else if (first && last)
       rs_scatter_kernel<RS_PAIR, RS_PAIR, true><<<g, b, 0, ctx->stream>>>(in, nullptr, n, shift, nblocks, offs->as<uint32_t>(), nullptr, perm, 0, 0);
     else if (first)
       rs_scatter_kernel<RS_PAIR, RS_PACKED, true><<<g, b, 0, ctx->stream>>>(in, nullptr, n, shift, nblocks, offs->as<uint32_t>(), out, nullptr, 0, 0);
@@ -298,6 +314,14 @@ void radix_sort_index_u32(Ctx *ctx, const uint32_t *keys, int64_t n, int bits, u
     in = out;
     out = (out == w0->as<uint64_t>() && w1) ? w1->as<uint64_t>() : w0->as<uint64_t>();
   }
+}
+
+void radix_sort_index_u32(Ctx *ctx, const uint32_t *keys, int64_t n, int bits, uint32_t *perm) {
+  sort_index_u32(ctx, keys, n, bits, perm, nullptr);
+}
+
+void radix_sort_gather_rows_u32(Ctx *ctx, const uint32_t *keys, int64_t n, int bits, const SortedRowsOut &ro) {
+  sort_index_u32(ctx, keys, n, bits, nullptr, &ro);
 }
 
 } // namespace sq
